@@ -8,7 +8,7 @@ beta in HBM.  Default workload = the configuration BASELINE.json's metric is quo
 EUR LD blocks, DBSLMM (large + small effects), h2 = 0.5 tuned over h2f in {0.8, 1.0, 1.2} (one
 Gram + three factorisations and solves per step).  --config 2 is the small configs[1] case.
 
-    python bench.py [--gpus N --steps K --warmup W] [--devices 0,0]
+    python bench.py [--gpus N --steps K --warmup W] [--devices 0,0] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Multi-GPU (strong scaling, the default): ONE problem -- the same workload as N=1 -- with its LD
@@ -27,6 +27,13 @@ value = the problem's SNPs x steps / time.  For N > 1 the merged betas of the la
 against the oracle's direct solve on every block >= 2000 SNPs (max_dbeta_vs_cpu_ref.big_blocks).
 --replicas (torchrun): N independent copies of the workload (seed = 1 + rank, no exchange) -> weak
 scaling.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (value, ms_per_step, the phase
+spans of the timed steps).  --full adds every leg that takes runs of its own: the CPU baseline and
+the beta checks against the oracle, the end-to-end CLI leg, the lead-group-off phase times and the
+multi-GPU rehearsal (--no-cpu-baseline, --no-check, --no-isolated, --no-e2e and --predict none
+switch single legs of a --full run off).  --dump-outputs DIR writes the betas and block status of
+the last timed step to DIR/<name>.npy (the inputs are seeded: two builds compare array for array).
 """
 from __future__ import annotations
 
@@ -81,6 +88,13 @@ def parse():
                     help="synthetic panel generator (default: numpy for config 2, gpu above)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="dbslmm_options field (path thresholds; experiments), repeatable")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: CPU baseline and beta checks "
+                         "against the oracle, end-to-end CLI, lead-group-off phase times, multi-GPU "
+                         "rehearsal (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (beta_s, beta_l, status: one row per "
+                         "h2f solve) to DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true",
                     help="N > 1: skip the big-block beta check of the merged betas")
@@ -112,7 +126,30 @@ def parse():
         a.predict = "2,4,8" if a.config == 4 and a.snps == CONFIGS[4]["snps"] else None
     elif a.predict == "none":
         a.predict = None
+    if not a.full:      # a plain run: only what the headline figure needs
+        a.no_cpu_baseline = a.no_check = a.no_isolated = a.no_e2e = True
+        a.predict = None
     return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: {name: array} -> outdir/<name>.npy as float64, at most DUMP_MAX_BYTES in all.
+    A larger set is cut to a fixed sample: the same seeded choice of flat indices (ascending) of
+    every array, each array keeping its share of the budget."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    budget = DUMP_MAX_BYTES - 1024 * len(arrays)        # .npy headers
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(a.size * (budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def kernel_roofline(name, ms, wl, n_solve=1):
@@ -486,7 +523,7 @@ def config1_main(args):
            "-b", blocks_f, "-n", "2400", "-nsnp", "996", "-h", "0.5", "-mafMax", "0.2", "-t", "1",
            "-eff", eff, "--precise-out", "--timing", "--repeat", str(args.warmup + args.steps)]
     runs = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 1):
         t1 = time.perf_counter()
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         wall = time.perf_counter() - t1
@@ -500,6 +537,18 @@ def config1_main(args):
     n_snp = int(ph["snps"])
     rows = [x.split() for x in open(eff + ".txt").read().splitlines() if x.strip()]
     got = np.array([float(x[2]) for x in rows])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"beta": got})
+    head = {
+        "metric": "SNPs solved/sec (whole node) + max-|\u0394\u03b2| vs CPU ref, test_dat chr1",
+        "value": n_snp / step_s, "unit": "SNPs/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "full": args.full,
+        "data": "the reference's test_dat chr1 example (tests/golden/test_dat, 400 individuals)",
+    }
+    if not args.full:
+        print(json.dumps(dict(head, cpu_baseline=None, end_to_end=None, max_dbeta_vs_cpu_ref=None)), flush=True)
+        return
 
     # CPU leg (the oracle = the C restatement of the reference; bench's cpu_baseline leg)
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -551,12 +600,7 @@ def config1_main(args):
     m_b = np.diff(s_ptr) + np.diff(l_ptr)
     flops = float(np.sum(n_ref * m_b * (m_b + 1.0) + m_b.astype(float) ** 3 / 3 + 2.0 * m_b ** 2))
     ach = flops / step_s / 1e12
-    out = {
-        "metric": "SNPs solved/sec (whole node) + max-|\u0394\u03b2| vs CPU ref, test_dat chr1",
-        "value": n_snp / step_s, "unit": "SNPs/s", "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": step_s * 1e3, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "the reference's test_dat chr1 example (tests/golden/test_dat, 400 individuals)",
+    out = dict(head, **{
         "config": {"workload": "test_dat chr1, DBSLMM tau 0.8, -n 2400 -nsnp 996 -h 0.5 -mafMax 0.2, EUR chr1 "
                                "blocks (BASELINE configs[0])", "snps": n_snp, "n_ref": n_ref, "blocks": nb,
                    "parallelism": "1 GPU (drop-in CLI)"},
@@ -572,7 +616,7 @@ def config1_main(args):
         "end_to_end": {"value": n_snp / wall, "unit": "SNPs/s", "seconds": wall, "phases_s": ph,
                        "note": "dbslmm CLI process wall time, HIP init included (second of two runs)"},
         "max_dbeta_vs_cpu_ref": {"vs_pcg": res["pcg"], "vs_direct": res["direct"], "snps_compared": int(got.size)},
-    }
+    })
     print(json.dumps(out), flush=True)
 
 
@@ -688,12 +732,11 @@ def main():
     wl = plan.workload()                      # + the h2f iteration count of the runs
     kms, nlaunch = plan.kernel_ms()
     kms = kms * nlaunch / args.steps          # per step (a tuning step is len(h2f) runs)
-    # the results of one more step, compared with the CPU reference below (every h2f solve)
+    # the results of the last timed step: what --dump-outputs writes and the --full legs compare
+    # with the CPU reference below (every h2f solve)
     if sigmas or sharded:
-        res = plan.run_multi(sig_run, out=outs)
-        res = [(a.copy(), b.copy(), c.copy()) for a, b, c in res]
+        res = [(outs[0][i].copy(), outs[1][i].copy(), outs[2][i].copy()) for i in range(n_copies)]
     else:
-        plan.run()
         res = [plan.download()]
     status = res[0][2]
     if sharded:   # this rank's units only: the other blocks' status entries are not its own
@@ -706,6 +749,13 @@ def main():
     st = torch.tensor([int(np.sum((status != 0) & (status != 1)))], dtype=torch.int64, device=cdev)
     if dist is not None:
         dist.all_reduce(st, op=dist.ReduceOp.SUM)
+
+    if rank == 0 and args.dump_outputs:
+        dres = full_res if full_res is not None else res
+        arrays = {"beta_s": np.stack([r[0] for r in dres]), "beta_l": np.stack([r[1] for r in dres])}
+        if dres[0][2] is not None:
+            arrays["status"] = np.stack([r[2] for r in dres])
+        dump_outputs(args.dump_outputs, arrays)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     snps = torch.tensor([wl["snps"]], dtype=torch.float64, device=cdev)
@@ -782,6 +832,7 @@ def main():
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak" if args.replicas else "strong", "vs_baseline": None, "dtype": "f64",
+            "full": args.full,
             "data": "synthetic (AR(1)-LD PLINK panel, seed = %s)" % ("1 + rank" if args.replicas else "1"),
             "config": {"workload": f"synthetic {args.snps} SNP x {args.n_ref} indiv, 22 chr "
                                    f"{args.pop} LD blocks, {'LMM-only' if args.lmm_only else 'DBSLMM large+small'}, "

@@ -19,6 +19,6 @@ step() {  # step <name> <timeout-s> <cmd...>
 }
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
-step bench 600 python bench.py --steps 20 --warmup 3
+step bench 600 python bench.py --full --steps 20 --warmup 3
 step rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --predict none
 echo done

@@ -8,7 +8,7 @@ O=gpurun_out/${GOUT:-r1}; mkdir -p $O
 run() { local to=$1; shift; timeout -k 10 "$to" "$@"; local rc=$?; [ $rc -eq 0 ] || { echo "FAILED rc=$rc: $*"; exit $rc; }; }
 run 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1
 run 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-run 400 python bench.py > $O/bench_c4.log 2>&1
+run 400 python bench.py --full > $O/bench_c4.log 2>&1
 tail -1 $O/bench_c4.log > $O/bench_c4.json
 B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --predict none --no-isolated --no-e2e"
 run 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c4 -o run -- $B > $O/c4_prof.log 2>&1
