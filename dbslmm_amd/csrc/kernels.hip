@@ -2,17 +2,22 @@
 //
 // The front of the hot path of DBSLMMFIT::est (reference scr/dbslmmfit.cpp:56-363):
 //
-//   dbslmm_unpack_stats  IO::readSNPIm + nomalizeVec statistics (scr/dtpr.cpp:285-380):
-//                        2-bit PLINK rows -> the 2-bit DOSAGE operand Gp (codes 0/1/2, 3 =
-//                        missing, padding individuals 0; kpad / 16 dwords per slot, slots in
-//                        block order) plus exact integer per-SNP count / sum / sum-of-squares
-//                        (popcounts) and the fp64 mean and 1/sd (N-1).  HBM-bound, one wave per
-//                        slot.
+//   dbslmm_bed_repitch   once per uploaded panel: the verbatim .bed (3 magic bytes, rows at any
+//                        byte) -> the resident panel IMAGE: row r at r * pitch, pitch = kpad / 4
+//                        bytes (a multiple of 64), every bit past individual n_ref - 1 set
+//                        (PLINK code 11 = dosage 0), plus one all-0xFF zero-dosage row at the
+//                        end.  Raw PLINK codes in file row order: no slot order, no decode.
+//   dbslmm_snp_stats     IO::readSNPIm + nomalizeVec statistics (scr/dtpr.cpp:285-380): exact
+//                        integer per-SNP count / sum / sum-of-squares (popcounts) of the image
+//                        rows of the plan's slots and the fp64 mean and 1/sd (N-1).  HBM-bound
+//                        (read only), one wave per slot.
 //   dbslmm_gram_i8 /     estBlock's LD matrices (scr/dbslmmfit.cpp:697-709, 751-756) as ONE
 //   dbslmm_gram_big /    joint Gram per block over [small | large] SNPs on the FP4 matrix cores
-//   dbslmm_gram_huge     (v_mfma_scale_f32_32x32x64_f8f6f4, exact integer sums in fp32; each Gp
-//                        dword is expanded to FP4 operands in registers -- fp4_chunk below; the
-//                        _i8 kernel keeps its round-2 name) with an fp64 epilogue that
+//   dbslmm_gram_huge     (v_mfma_scale_f32_32x32x64_f8f6f4, exact integer sums in fp32; the
+//                        operand rows are gathered from the image by slot_pos and each raw dword
+//                        is expanded to FP4 operands in registers -- the raw form, fp4_chunk_raw
+//                        / gram_exact below; the _i8 kernel keeps its round-2 name) with an fp64
+//                        epilogue that
 //                        centres, standardises and applies tau:
 //                          Sigma_ij = tau/n_ref * C_ij /(s_i s_j) + (1-tau) delta_ij,
 //                          C_ij = G_ij - S_i S_j / n   (no missing calls in the block)
@@ -53,30 +58,27 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// 4 bytes starting at an arbitrary byte offset, from two aligned dword loads.
-// The .bed image keeps its 3 magic bytes so row starts are generally unaligned.
-__device__ __forceinline__ uint32_t load_u32_any(const uint8_t* __restrict__ base, int64_t off) {
-    const int64_t a = off & ~int64_t(3);
-    const uint32_t w0 = *reinterpret_cast<const uint32_t*>(base + a);
-    const uint32_t w1 = *reinterpret_cast<const uint32_t*>(base + a + 4);
-    return __builtin_amdgcn_alignbyte(w1, w0, static_cast<uint32_t>(off & 3));
+// The 2-bit DOSAGE codes (0, 1, 2) of one raw image dword (PLINK codes, individual j in bits
+// 2j..2j+1; 00 -> 2, 10 -> 1, 11 -> 0): d = 2 - (w - (w >> 1 & 1)) per field.  Every field of the
+// subtrahend is 0, 1 or 2, so no borrow crosses a field.  The missing code 01 comes out as 1: only
+// blocks without a missing call could take this form; it serves the missing-call path
+// (split_missing) -- the main loops skip the decode altogether (the raw form below).
+__device__ __forceinline__ uint32_t dose_code16(uint32_t w) {
+    return 0xAAAAAAAAu - (w - ((w >> 1) & 0x55555555u));
 }
-
-// The Gram operand Gp: per slot, kpad / 16 dwords of 2-bit DOSAGE codes (0, 1, 2; 3 = missing;
-// padding individuals 0), re-coded from the PLINK codes of one .bed dword (individual j in bits
-// 2j..2j+1; 00 -> 2, 10 -> 1, 11 -> 0, 01 -> missing: d0 = lo ^ hi, d1 = ~hi).  A quarter of the
-// bytes of an int8 operand; the Gram kernels expand it to FP4 on the fly (fp4_chunk).
-__device__ __forceinline__ uint32_t dose_code16(uint32_t w, uint32_t valid_mask_2bit) {
-    const uint32_t lo = w & 0x55555555u, hi = (w >> 1) & 0x55555555u;
-    const uint32_t d0 = (lo ^ hi) & valid_mask_2bit, d1 = ~hi & valid_mask_2bit;
-    return d0 | (d1 << 1);
+// image row of a block-local slot index li (block rows row0 .., m of them): rows past the block
+// and padding slots read the zero-dosage row zrow, so no load leaves the image
+__device__ __forceinline__ int64_t image_row(const int32_t* __restrict__ slot_pos, int row0, int li, int m,
+                                             int32_t zrow) {
+    const int32_t pos = li < m ? slot_pos[row0 + li] : -1;
+    return pos < 0 ? zrow : pos;
 }
 // The Gram kernels multiply on the FP4 matrix cores: dosages 0 / 1 / 2 (and the 0 / 1 masks of
 // the missing-call form) are exact e2m1 values, every product is exact and every partial sum an
 // integer below 4 n_ref < 2^24, so v_mfma_scale_f32_32x32x64_f8f6f4 gives the integer Gram bit for
-// bit -- at twice the MACs per clock of v_mfma_i32_32x32x32_i8, with half its operand bytes.  A Gp
-// dword (16 two-bit codes c) becomes two FP4 dwords with one mask each and one shift per PAIR of
-// dwords: w & 0x33333333 leaves the even-numbered codes in bits 0-1 of the nibbles, which as e2m1
+// bit -- at twice the MACs per clock of v_mfma_i32_32x32x32_i8, with half its operand bytes.  A
+// dosage-code dword (16 two-bit codes c) becomes two FP4 dwords with one mask each and one shift
+// per PAIR of dwords: w & 0x33333333 leaves the even-numbered codes in bits 0-1 of the nibbles, which as e2m1
 // read 0.5 c (0.0 / 0.5 / 1.0); (w >> 2) & 0x33333333 the odd ones (one 64-bit shift serves both
 // dwords of a pair -- the bits shifted in from the high dword are masked off).  The E8M0 block
 // scales 2^1 on both operands restore c_a c_b exactly.  (A fixed permutation of the individuals,
@@ -85,7 +87,7 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 constexpr int kE8M0Two = static_cast<int>(0x80808080u);   // E8M0 scale 2^1 in every byte
 constexpr uint32_t kFp4Mask = 0x33333333u;
-// 16 B of FP4 operand (32 individuals) from Gp dwords w0, w1
+// 16 B of FP4 operand (32 individuals) from dosage-code dwords w0, w1
 __device__ __forceinline__ v4i fp4_chunk(uint32_t w0, uint32_t w1) {
     const uint64_t t = ((static_cast<uint64_t>(w1) << 32) | w0) >> 2;
     return v4i{static_cast<int>(w0 & kFp4Mask), static_cast<int>(static_cast<uint32_t>(t) & kFp4Mask),
@@ -96,36 +98,65 @@ __device__ __forceinline__ v16f mfma_fp4(v4i a, v4i b, v16f c) {
     const v8i a8{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8{b[0], b[1], b[2], b[3], 0, 0, 0, 0};
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, kE8M0Two, 0, kE8M0Two);
 }
+// The RAW form (blocks without a missing call: the Gram kernels' main loops).  Decoding every dword
+// (dose_code16) costs ~4 VALU per dword on top of the expansion and made the Gram VALU-bound, so
+// the main loops skip it: bit 2 set in every nibble, (w & 0x33333333) | 0x44444444, makes e2m1
+// read the raw PLINK codes 00 / 10 / 11 as 2 / 4 / 6, and with E8M0 scales 2^-1 on both operands
+// an individual contributes v = 3 - g in {1, 2, 3} (g its dosage; padding individuals read 3).
+// The accumulator holds T_ab = sum_k v_a v_b over all kpad columns -- integers, 9 kpad < 2^24, so
+// exact in fp32 -- and the epilogues recover the same exact integer Gram before anything else
+// uses it (gram_exact, in int32: a row term 3 S_a - 9 kpad and a column term 3 S_b formed once
+// per row / column, one conversion and one add3 per element):
+//     G_ab = T_ab - 9 kpad + 3 (S_a + S_b),  S the integer dosage sums of dbslmm_snp_stats.
+// k44 = 0x44444444 is held in a VGPR (gfx9 VOP3 takes one scalar operand and no literal): one
+// v_and_or_b32 per FP4 dword, no more VALU than the decoded form's plain mask.
+constexpr int kE8M0Half = 0x7E7E7E7E;                      // E8M0 scale 2^-1 in every byte
+__device__ __forceinline__ uint32_t raw_k44() {
+    uint32_t k = 0x44444444u;
+    asm volatile("" : "+v"(k));
+    return k;
+}
+__device__ __forceinline__ v4i fp4_chunk_raw(uint32_t w0, uint32_t w1, uint32_t k44) {
+    const uint64_t t = ((static_cast<uint64_t>(w1) << 32) | w0) >> 2;
+    return v4i{static_cast<int>((w0 & kFp4Mask) | k44), static_cast<int>((static_cast<uint32_t>(t) & kFp4Mask) | k44),
+               static_cast<int>((w1 & kFp4Mask) | k44), static_cast<int>((static_cast<uint32_t>(t >> 32) & kFp4Mask) | k44)};
+}
+__device__ __forceinline__ v16f mfma_fp4_raw(v4i a, v4i b, v16f c) {
+    const v8i a8{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8{b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, kE8M0Half, 0, kE8M0Half);
+}
+// the exact integer Gram entry from the raw-form sum t: row term ri = 3 S_i - 9 kpad (gram_row),
+// column term cj = 3 S_j (gram_col); t < 2^24 and |ri|, cj < 2^27, so int32 holds every term
+__device__ __forceinline__ int gram_row(double s, int64_t kpad) { return 3 * static_cast<int>(s) - 9 * static_cast<int>(kpad); }
+__device__ __forceinline__ int gram_col(double s) { return 3 * static_cast<int>(s); }
+__device__ __forceinline__ int gram_exact(float t, int ri, int cj) { return static_cast<int>(t) + ri + cj; }
 // centred Gram entry C_ij = G_ij - S_i S_j / n, as G - (S_i S_j) (1 / n) in one fma: S_i S_j is
 // an exact integer (below 2^53), the product with the rounded reciprocal replaces an fp64 divide
 // per element (relative deviation from the divided form ~1e-16 of S_i S_j / n)
-__device__ __forceinline__ double centre(float g, double sisj, double rn) {
-    return __builtin_fma(-sisj, rn, static_cast<double>(g));
+__device__ __forceinline__ double centre(double g, double sisj, double rn) {
+    return __builtin_fma(-sisj, rn, g);
 }
-// missing-call form of a Gp dword (code 3 = missing): g = the dosages with missing calls as 0,
-// o = 1 for observed calls (padding individuals count as observed: pad_k in the epilogue)
-__device__ __forceinline__ void split_missing(uint32_t x, uint32_t& g, uint32_t& o) {
-    const uint32_t m2 = x & (x >> 1) & 0x55555555u;
-    g = x & ~(3u * m2);
+// missing-call form of a raw image dword (PLINK code 01 = missing): g = the dosage codes with
+// missing calls as 0, o = 1 for observed calls (padding individuals read 11: observed, dosage 0 --
+// pad_k in the epilogue)
+__device__ __forceinline__ void split_missing(uint32_t w, uint32_t& g, uint32_t& o) {
+    const uint32_t m2 = w & ~(w >> 1) & 0x55555555u;
+    g = dose_code16(w) & ~(3u * m2);
     o = m2 ^ 0x55555555u;
 }
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
-// Kernel 1: unpack + per-SNP statistics.  One wave per slot (SNP row of a block), 4 waves/WG.
-//   Gp (optional)  [n_slots][kpad / 16] dosage-code dwords (dose_code16); padding slots (pos < 0)
-//                  and padding individuals are dosage 0.
-//   stat_*         exact integer statistics over the n_ref individuals.
-//   mu, rsd, S     fp64: mean over observed calls (= the imputation value, dtpr.cpp:358),
-//                  1/sd with the N-1 divisor (nomalizeVec), sum of observed dosages.
-//   block_flags    bit 0 set when a slot of the block has a missing call.
-//   slot_list      optional: unpack only these n_slots slots (the plan unpacks its lead group first)
-// A row starts at any byte (3 + pos * bytes_per_snp): lane q of a pass handles the row's 16-B
+// Kernel 0: the resident panel image from the verbatim .bed upload.  One wave per image row, 4
+// waves/WG; rows [0, n_rows) are the file's rows, row n_rows is the zero-dosage row (all 0xFF)
+// that padding slots and tile rows past a block read.
+// A file row starts at any byte (3 + r * bytes_per_snp): lane q of a pass builds the row's 16-B
 // chunk q (64 individuals) from the two aligned 16-B loads covering it (the second only when the
-// row is not 16-B aligned), so a wave issues whole-dwordx4 loads for its row up front, kU chunks
-// per lane, and writes dwordx4 stores.  The image is followed by kBedPad (64) allocated bytes, so
-// the last row's loads stay inside the allocation; bytes past n_ref are masked.
+// row is not 16-B aligned) and writes one dwordx4.  The upload is followed by kBedPad (64)
+// allocated bytes, so the last row's loads stay inside the allocation.  Bits past individual
+// n_ref - 1 (the pad bits of the last data byte and every byte up to the pitch) are set: PLINK
+// code 11 = dosage 0, observed -- whatever the file holds there.
 // ------------------------------------------------------------------------------------------
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u4v load_u4(const uint8_t* p) { return *reinterpret_cast<const u4v*>(p); }
@@ -145,10 +176,53 @@ __device__ __forceinline__ u4v shift_pair(u4v x, u4v y, int d, int bs) {
     return r;
 }
 
-extern "C" __global__ __launch_bounds__(256) void dbslmm_unpack_stats(
-    const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp,
+extern "C" __global__ __launch_bounds__(256) void dbslmm_bed_repitch(
+    const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp, int32_t n_rows,
+    uint8_t* __restrict__ img, int64_t pitch) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int r = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+    if (r > n_rows) return;
+    u4v* out = reinterpret_cast<u4v*>(img + static_cast<int64_t>(r) * pitch);
+    const int nq = static_cast<int>(pitch / 16);           // 16-B chunks of the image row
+    if (r == n_rows) {                                      // the zero-dosage row
+        for (int q = lane; q < nq; q += kWave) out[q] = u4v{~0u, ~0u, ~0u, ~0u};
+        return;
+    }
+    const int64_t row_off = 3 + static_cast<int64_t>(r) * bytes_per_snp;
+    const uint8_t* base = bed + (row_off & ~int64_t(15));
+    const int sh = static_cast<int>(row_off & 15), dsh = sh >> 2, bsh = sh & 3;
+    const int nqd = (n_ref + 63) / 64;          // chunks holding individuals
+    for (int q = lane; q < nq; q += kWave) {
+        u4v g = u4v{~0u, ~0u, ~0u, ~0u};
+        if (q < nqd) {
+            const u4v lo = load_u4(base + 16 * static_cast<int64_t>(q));
+            const u4v wv = sh ? shift_pair(lo, load_u4(base + 16 * static_cast<int64_t>(q) + 16), dsh, bsh) : lo;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int nv = min(16, max(0, n_ref - (64 * q + 16 * j)));
+                const uint32_t keep = nv >= 16 ? ~0u : (1u << (2 * nv)) - 1u;
+                g[j] = wv[j] | ~keep;
+            }
+        }
+        out[q] = g;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Kernel 1: per-SNP statistics of image rows.  One wave per slot (SNP row of a block), 4 waves/WG.
+//   mu, rsd, S     fp64: mean over observed calls (= the imputation value, dtpr.cpp:358),
+//                  1/sd with the N-1 divisor (nomalizeVec), sum of observed dosages -- from the
+//                  exact integer count / sum / sum of squares over the n_ref individuals.
+//   block_flags    bit 0 set when a slot of the block has a missing call.
+//   slot_list      optional: only these n_slots slots (the plan takes its lead group first)
+// Image rows are 64-B aligned and their bits past n_ref read 11 (neither missing nor a dosage),
+// so lane q of a pass takes the row's 16-B chunk q (64 individuals) with one dwordx4 load, kU
+// chunks per lane in flight, and no popcount needs a tail mask.  Nothing but the statistics is
+// written: the Gram kernels read the image rows themselves.
+// ------------------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256) void dbslmm_snp_stats(
+    const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
     const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
-    uint32_t* __restrict__ Gp, int64_t kpad,
     double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
     int32_t* __restrict__ block_flags, const int32_t* __restrict__ slot_list) {
     constexpr int kU = 4;                       // chunks per lane per pass (loads in flight)
@@ -156,13 +230,8 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_unpack_stats(
     const int k = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     if (k >= n_slots) return;
     const int slot = slot_list ? slot_list[k] : k;   // a subset of the slots (n_slots of them)
-    const int32_t pos = slot_pos ? slot_pos[slot] : slot;   // (null: slot k reads bed row k)
-    const int64_t n_words = kpad / 16;          // 16 individuals per dword (kpad: a multiple of 64)
-    const int nq = static_cast<int>(n_words / 4);           // 16-B chunks of the Gp row
-    u4v* grow = Gp ? reinterpret_cast<u4v*>(Gp + static_cast<int64_t>(slot) * n_words) : nullptr;
+    const int32_t pos = slot_pos ? slot_pos[slot] : slot;   // (null: slot k reads image row k)
     if (pos < 0) {                              // padding slot
-        if (grow)
-            for (int q = lane; q < nq; q += kWave) grow[q] = u4v{0u, 0u, 0u, 0u};
         if (lane == 0) {
             if (S_out) S_out[slot] = 0.0;
             if (mu_out) mu_out[slot] = 0.0;
@@ -170,54 +239,38 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_unpack_stats(
         }
         return;
     }
-    const int64_t row_off = 3 + static_cast<int64_t>(pos) * bytes_per_snp;
-    const uint8_t* base = bed + (row_off & ~int64_t(15));
-    const int sh = static_cast<int>(row_off & 15), dsh = sh >> 2, bsh = sh & 3;
-    const int nqd = (n_ref + 63) / 64;          // chunks holding individuals
-    int cnt = 0, sum = 0, sq = 0, nmiss = 0;
-    for (int q0 = 0; q0 < nq; q0 += kWave * kU) {
-        u4v lo[kU], hi[kU];
+    const uint8_t* base = img + static_cast<int64_t>(pos) * pitch;
+    const int nqd = (n_ref + 63) / 64;          // chunks holding individuals (<= pitch / 16)
+    int sum = 0, sq = 0, nmiss = 0;
+    for (int q0 = 0; q0 < nqd; q0 += kWave * kU) {
+        u4v wv[kU];
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const int q = q0 + kWave * u + lane;
-            lo[u] = hi[u] = u4v{0u, 0u, 0u, 0u};
-            if (q < nqd) {
-                lo[u] = load_u4(base + 16 * static_cast<int64_t>(q));
-                if (sh) hi[u] = load_u4(base + 16 * static_cast<int64_t>(q) + 16);
-            }
+            wv[u] = u4v{~0u, ~0u, ~0u, ~0u};
+            if (q < nqd) wv[u] = load_u4(base + 16 * static_cast<int64_t>(q));
         }
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            const int q = q0 + kWave * u + lane;
-            if (q >= nq) break;
-            const u4v wv = sh ? shift_pair(lo[u], hi[u], dsh, bsh) : lo[u];
-            u4v g;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int first = 64 * q + 16 * j;
-                const int nv = min(16, max(0, n_ref - first));
-                const uint32_t vmask = nv >= 16 ? 0x55555555u : ((1u << (2 * nv)) - 1u) & 0x55555555u;
-                const uint32_t word = wv[j];
-                const uint32_t lo2 = word & vmask;
-                const uint32_t hi2 = (word >> 1) & vmask;
+                const uint32_t word = wv[u][j];
+                const uint32_t lo2 = word & 0x55555555u;
+                const uint32_t hi2 = (word >> 1) & 0x55555555u;
                 const int n_miss = __builtin_popcount(lo2 & ~hi2);
-                const int n_two = __builtin_popcount(~lo2 & ~hi2 & vmask);
+                const int n_two = __builtin_popcount(~lo2 & ~hi2 & 0x55555555u);
                 const int n_one = __builtin_popcount(~lo2 & hi2);
                 nmiss += n_miss;
-                cnt += __builtin_popcount(vmask) - n_miss;
                 sum += 2 * n_two + n_one;
                 sq += 4 * n_two + n_one;
-                g[j] = dose_code16(word, vmask);
             }
-            if (grow) grow[q] = g;
         }
     }
-    cnt = wave_sum_i32(cnt);
     sum = wave_sum_i32(sum);
     sq = wave_sum_i32(sq);
     nmiss = wave_sum_i32(nmiss);
     if (lane == 0) {
-        const double dc = static_cast<double>(cnt);
+        const double dc = static_cast<double>(n_ref - nmiss);       // observed calls
         const double ds = static_cast<double>(sum);
         const double mu = ds / dc;                                   // imputation value
         const double css = static_cast<double>(sq) - ds * ds / dc;  // centred sum of squares
@@ -231,18 +284,18 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_unpack_stats(
 
 // ------------------------------------------------------------------------------------------
 // MAF of IO::readSNPIm as the reference rounds it (dtpr.cpp:356-362): missing calls take the
-// mean of the observed calls (mu, exact S / count from dbslmm_unpack_stats), sum(geno) runs in
+// mean of the observed calls (mu, exact S / count from dbslmm_snp_stats), sum(geno) runs in
 // Armadillo's arrayops::accumulate order -- two sequential accumulators over the even / odd
 // individuals -- and af = 0.5 * sum / n.  Once a (non-integer) mean has been added, each later add
 // rounds, so the order decides the last bits, and the MAF filter of matchRef (|maf_ref - maf| <
 // mafMax, strict) can flip on them.  One thread per row: a sequential chain of n_ref fp64 adds,
 // rounded exactly like the host's (no reassociation).
 // ------------------------------------------------------------------------------------------
-// Rows without a missing call (miss[k] == 0; miss / S from dbslmm_unpack_stats, optional) hold
+// Rows without a missing call (miss[k] == 0; miss / S from dbslmm_snp_stats, optional) hold
 // only integer dosages: every partial sum of that order is an exact integer, so a1 + a2 equals
 // the exact observed sum S and the chain is skipped (bit-identical).
 extern "C" __global__ __launch_bounds__(256) void dbslmm_maf_arma(
-    const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp,
+    const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
     const int32_t* __restrict__ pos, int32_t n_rows, const double* __restrict__ mu,
     double* __restrict__ maf_out, const double* __restrict__ S, const int32_t* __restrict__ miss) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -252,11 +305,11 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_maf_arma(
         maf_out[k] = (1.0 - af) < af ? 1.0 - af : af;
         return;
     }
-    const int64_t row_off = 3 + static_cast<int64_t>(pos ? pos[k] : k) * bytes_per_snp;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(img + static_cast<int64_t>(pos ? pos[k] : k) * pitch);
     const double m = mu[k];
     double a1 = 0.0, a2 = 0.0;
     for (int32_t i0 = 0; i0 < n_ref; i0 += 16) {
-        const uint32_t word = load_u32_any(bed, row_off + i0 / 4);
+        const uint32_t word = row[i0 / 16];
         const int nv = min(16, n_ref - i0);
         for (int j = 0; j < nv; j += 2) {          // i0 is even: j even = even individual
             const uint32_t c0 = (word >> (2 * j)) & 3u;
@@ -275,7 +328,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_maf_arma(
 // ------------------------------------------------------------------------------------------
 // Kernel 2: grouped joint Gram on FP4 MFMA.  One wave = one 32x32 output tile (block, ti, tj),
 // ti >= tj, K loop over the padded individuals 128 at a time (gram_tile32 below: each lane
-// loads 4 Gp dwords of its row per operand and feeds two FP4 MFMAs; identical k-permutation on
+// loads 4 image dwords of its row per operand and feeds two FP4 MFMAs; identical k-permutation on
 // the A and B side, so any lane->k assignment the instruction uses is summed consistently).
 // Output: row-major lower triangle of the block's joint matrix
 //     Sigma (no d shift; the Cholesky kernel adds 1/(sigma_s n) on the small diagonal).
@@ -293,31 +346,36 @@ __device__ __forceinline__ int copy_hi(int m, int32_t tmin, int32_t tcopy, int32
 }
 
 // One 32 x 32 output tile (rows r0.., cols c0.. of block-local slots) on one wave, K over all
-// kpad individuals with operands straight from Gp (L2), FP4 MFMAs.  Per 128 individuals (8 Gp
-// dwords) lane (row, h = lane >> 5) loads dwords 4 h .. 4 h + 3 of its row and feeds dwords
+// kpad individuals with operands straight from the image rows of its slots (L2; rows past m: the
+// zero-dosage row), FP4 MFMAs.  Per 128 individuals (8 image dwords) lane (row, h = lane >> 5)
+// loads dwords 4 h .. 4 h + 3 of its row and feeds (raw form; missing: decoded, split_missing) dwords
 // 4 h + 2 s, 4 h + 2 s + 1 to MFMA s: both operands use the same individual -> k map, so every
 // product sums each individual once.  missing: the four products GG, GO, OG, OO of the
 // observed-call expansion.
 __device__ __forceinline__ void gram_tile32(
-    const uint32_t* __restrict__ Gp, int64_t kpad, int row0, int m, int ld, int64_t moff, bool missing,
+    const uint8_t* __restrict__ img, int64_t kpad, const int32_t* __restrict__ slot_pos, int32_t zrow,
+    int row0, int m, int ld, int64_t moff, bool missing,
     int r0, int c0, int lane, const double* __restrict__ S, const double* __restrict__ mu,
     const double* __restrict__ rsd, double n_ref_d, double pad_k, double tau, double* __restrict__ M,
     int32_t ncopy, int64_t cstride, int32_t tmin, int32_t tcopy, uint16_t* __restrict__ G16,
     int64_t g16off, int64_t g16ld) {
-    const int64_t kw = kpad / 16;                 // Gp dwords per slot (kpad: a multiple of 256)
-    const uint32_t* pa = Gp + static_cast<int64_t>(row0 + r0 + (lane & 31)) * kw + 4 * (lane >> 5);
-    const uint32_t* pb = Gp + static_cast<int64_t>(row0 + c0 + (lane & 31)) * kw + 4 * (lane >> 5);
+    const int64_t kw = kpad / 16;                 // image dwords per row (kpad: a multiple of 256)
+    const uint32_t* pa = reinterpret_cast<const uint32_t*>(img) +
+                         image_row(slot_pos, row0, r0 + (lane & 31), m, zrow) * kw + 4 * (lane >> 5);
+    const uint32_t* pb = reinterpret_cast<const uint32_t*>(img) +
+                         image_row(slot_pos, row0, c0 + (lane & 31), m, zrow) * kw + 4 * (lane >> 5);
 
     v16f acc = {0.0f};
     v16f acc_go = {0.0f}, acc_og = {0.0f}, acc_oo = {0.0f};
-    if (!missing) {
+    if (!missing) {   // raw form: acc = T (gram_exact in the epilogue)
+        const uint32_t k44 = raw_k44();
         for (int64_t w = 0; w < kw; w += 8) {
             const v4i wa = *reinterpret_cast<const v4i*>(pa + w);
             const v4i wb = *reinterpret_cast<const v4i*>(pb + w);
 #pragma unroll
             for (int q = 0; q < 2; ++q)
-                acc = mfma_fp4(fp4_chunk(static_cast<uint32_t>(wa[2 * q]), static_cast<uint32_t>(wa[2 * q + 1])),
-                               fp4_chunk(static_cast<uint32_t>(wb[2 * q]), static_cast<uint32_t>(wb[2 * q + 1])), acc);
+                acc = mfma_fp4_raw(fp4_chunk_raw(static_cast<uint32_t>(wa[2 * q]), static_cast<uint32_t>(wa[2 * q + 1]), k44),
+                                   fp4_chunk_raw(static_cast<uint32_t>(wb[2 * q]), static_cast<uint32_t>(wb[2 * q + 1]), k44), acc);
         }
     } else {
         for (int64_t w = 0; w < kw; w += 8) {
@@ -343,16 +401,19 @@ __device__ __forceinline__ void gram_tile32(
     // fp64 epilogue.  C/D map of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8(r>>2) + 4(lane>>5)
     const int j = lane & 31;
     const int lj = c0 + j;
+    const int sj = row0 + lj;
+    const double Sj = lj < m ? S[sj] : 0.0;
+    const int cj = gram_col(Sj);
     if (G16 && !missing) {   // PCG route: the exact integer Gram (pcg.hip forms Sigma around it)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int li = r0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (li < m && lj < m) G16[g16off + li * g16ld + lj] = static_cast<uint16_t>(acc[r]);
+            if (li < m && lj < m)
+                G16[g16off + li * g16ld + lj] =
+                    static_cast<uint16_t>(gram_exact(acc[r], gram_row(S[row0 + li], kpad), cj));
         }
         return;
     }
-    const int sj = row0 + lj;
-    const double Sj = lj < m ? S[sj] : 0.0;
     const double muj = lj < m ? mu[sj] : 0.0;
     const double rj = lj < m ? rsd[sj] : 0.0;
     const double scale = tau / n_ref_d, rn = 1.0 / n_ref_d;
@@ -364,7 +425,7 @@ __device__ __forceinline__ void gram_tile32(
         const int si = row0 + li;
         double c;
         if (!missing) {
-            c = centre(acc[r], S[si] * Sj, rn);
+            c = centre(static_cast<double>(gram_exact(acc[r], gram_row(S[si], kpad), cj)), S[si] * Sj, rn);
         } else {
             const double mui = mu[si];
             c = static_cast<double>(acc[r]) - muj * static_cast<double>(acc_go[r]) -
@@ -379,7 +440,7 @@ __device__ __forceinline__ void gram_tile32(
 }
 
 extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_i8(
-    const uint32_t* __restrict__ Gp, int64_t kpad,
+    const uint8_t* __restrict__ img, int64_t kpad, const int32_t* __restrict__ slot_pos, int32_t zrow,
     const GramTile* __restrict__ tiles, int32_t n_tiles,
     const int32_t* __restrict__ blk_row0, const int32_t* __restrict__ blk_m,
     const int32_t* __restrict__ blk_ld, const int64_t* __restrict__ blk_matoff,
@@ -393,7 +454,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_i8(
     if (t >= n_tiles) return;
     const GramTile tile = tiles[t];
     const int b = tile.block;
-    gram_tile32(Gp, kpad, blk_row0[b], blk_m[b], blk_ld[b], blk_matoff[b], (block_flags[b] & 1) != 0,
+    gram_tile32(img, kpad, slot_pos, zrow, blk_row0[b], blk_m[b], blk_ld[b], blk_matoff[b], (block_flags[b] & 1) != 0,
                 kTile * tile.ti, kTile * tile.tj, lane, S, mu, rsd, n_ref_d, pad_k, tau, M, ncopy, cstride,
                 tmin, tcopy, G16, G16 ? g16off[b] : 0, G16 ? g16ld[b] : 0);
 }
@@ -407,7 +468,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_i8(
 // current stage's 16 MFMAs per wave.  Diagonal tiles stage one operand and skip the
 // strictly-upper quadrant.  Tiles come in per-XCD queues (entry e runs on XCD e % 8) so a block's
 // rows stay in one L2; entries with block < 0 are padding.  Blocks with a missing call (flag set
-// by the unpack) take the exact 4-product 32 x 32 path.
+// by the statistics pass) take the exact 4-product 32 x 32 path.
 // ------------------------------------------------------------------------------------------
 namespace gram {
 constexpr int kGT = 128;                  // output tile edge
@@ -418,7 +479,7 @@ constexpr int kLdsBytes = 2 * 2 * kOpBytes;   // 2 stages x (A, B) = 73,728 B
 }  // namespace gram
 
 extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
-    const uint32_t* __restrict__ Gp, int64_t kpad,
+    const uint8_t* __restrict__ img, int64_t kpad, const int32_t* __restrict__ slot_pos, int32_t zrow,
     const GramTile* __restrict__ tiles, int32_t n_tiles,
     const int32_t* __restrict__ blk_row0, const int32_t* __restrict__ blk_m,
     const int32_t* __restrict__ blk_ld, const int64_t* __restrict__ blk_matoff,
@@ -443,27 +504,34 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
             if (diag && sj > si) continue;
             const int r0 = kGT * tile.ti + 32 * si, c0 = kGT * tile.tj + 32 * sj;
             if (r0 >= m || c0 >= m) continue;
-            gram_tile32(Gp, kpad, row0, m, ld, moff, true, r0, c0, lane, S, mu, rsd, n_ref_d, pad_k,
+            gram_tile32(img, kpad, slot_pos, zrow, row0, m, ld, moff, true, r0, c0, lane, S, mu, rsd, n_ref_d, pad_k,
                         tau, M, ncopy, cstride, tmin, tcopy, nullptr, 0, 0);
         }
         return;
     }
     const int64_t kw = kpad / 16;
-    const uint32_t* ga = Gp + static_cast<int64_t>(row0 + kGT * tile.ti) * kw;
-    const uint32_t* gb = Gp + static_cast<int64_t>(row0 + kGT * tile.tj) * kw;
-    // staging map: 128 rows x 16 Gp dwords (16 individuals each) per operand and stage; thread t
+    // staging map: 128 rows x 16 image dwords (16 individuals each) per operand and stage; thread t
     // moves dword pairs e = t + 256 q (row e >> 3, pair e & 7) and expands each pair to one 16-B
-    // FP4 chunk on the way into LDS.  Two register sets: the global loads of stage s + 2 are
-    // issued before stage s's MFMAs.
+    // FP4 chunk (raw form) on the way into LDS.  Two register sets: the global loads of stage s + 2
+    // are issued before stage s's MFMAs.  The row pointers (the image rows of the tile's slots;
+    // rows past m: the zero-dosage row) are formed once per tile.
     typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+    const uint32_t *ga[4], *gb[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = q * 256 + tid, r = e >> 3, c = e & 7;
+        ga[q] = reinterpret_cast<const uint32_t*>(img) + image_row(slot_pos, row0, kGT * tile.ti + r, m, zrow) * kw + 2 * c;
+        gb[q] = diag ? ga[q]
+                     : reinterpret_cast<const uint32_t*>(img) + image_row(slot_pos, row0, kGT * tile.tj + r, m, zrow) * kw + 2 * c;
+    }
+    const uint32_t k44 = raw_k44();             // raw form: acc = T (gram_exact in the epilogues)
     u2 ra0[4], rb0[4], ra1[4], rb1[4];
     auto gload = [&](u2 (&ra)[4], u2 (&rb)[4], int st) {
         const int64_t w0 = static_cast<int64_t>(st) * (kKS / 16);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int e = q * 256 + tid, r = e >> 3, c = e & 7;
-            ra[q] = *reinterpret_cast<const u2*>(ga + static_cast<int64_t>(r) * kw + w0 + 2 * c);
-            if (!diag) rb[q] = *reinterpret_cast<const u2*>(gb + static_cast<int64_t>(r) * kw + w0 + 2 * c);
+            ra[q] = *reinterpret_cast<const u2*>(ga[q] + w0);
+            if (!diag) rb[q] = *reinterpret_cast<const u2*>(gb[q] + w0);
         }
     };
     auto lstore = [&](const u2 (&ra)[4], const u2 (&rb)[4], int buf) {
@@ -472,8 +540,8 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int e = q * 256 + tid, r = e >> 3, c = e & 7;
-            *reinterpret_cast<v4i*>(A + r * kRS + 16 * c) = fp4_chunk(ra[q][0], ra[q][1]);
-            if (!diag) *reinterpret_cast<v4i*>(B + r * kRS + 16 * c) = fp4_chunk(rb[q][0], rb[q][1]);
+            *reinterpret_cast<v4i*>(A + r * kRS + 16 * c) = fp4_chunk_raw(ra[q][0], ra[q][1], k44);
+            if (!diag) *reinterpret_cast<v4i*>(B + r * kRS + 16 * c) = fp4_chunk_raw(rb[q][0], rb[q][1], k44);
         }
     };
     const int wr = wave >> 1, wc = wave & 1;
@@ -498,10 +566,10 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
             const v4i a1 = *reinterpret_cast<const v4i*>(pa + 32 * kRS + kk);
             const v4i b0 = *reinterpret_cast<const v4i*>(pb + kk);
             const v4i b1 = *reinterpret_cast<const v4i*>(pb + 32 * kRS + kk);
-            acc[0][0] = mfma_fp4(a0, b0, acc[0][0]);
-            acc[0][1] = mfma_fp4(a0, b1, acc[0][1]);
-            acc[1][0] = mfma_fp4(a1, b0, acc[1][0]);
-            acc[1][1] = mfma_fp4(a1, b1, acc[1][1]);
+            acc[0][0] = mfma_fp4_raw(a0, b0, acc[0][0]);
+            acc[0][1] = mfma_fp4_raw(a0, b1, acc[0][1]);
+            acc[1][0] = mfma_fp4_raw(a1, b0, acc[1][0]);
+            acc[1][1] = mfma_fp4_raw(a1, b1, acc[1][1]);
         }
     };
     const int nst = static_cast<int>(kpad / kKS);
@@ -522,23 +590,35 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
         if (st + 2 < nst) lstore(ra0, rb0, 0);
         __syncthreads();
     }
-    if (idle) return;
     if (G16) {   // PCG route: the exact integer Gram
+        // gram_exact's row and column terms of the tile go through LDS (the K loop's last barrier
+        // has passed: no wave reads the stages any more), so the element loop issues no global loads
+        int* eTerm = reinterpret_cast<int*>(glds);   // [128 row terms | 128 column terms]
+        {
+            const int col = tid >> 7, idx = kGT * (col ? tile.tj : tile.ti) + (tid & 127);
+            const double sv = idx < m ? S[row0 + idx] : 0.0;
+            eTerm[tid] = col ? gram_col(sv) : gram_row(sv, kpad);
+        }
+        __syncthreads();
+        if (idle) return;
         const int64_t go = g16off[b], gl = g16ld[b];
 #pragma unroll
         for (int sj = 0; sj < 2; ++sj) {
-            const int lj = kGT * tile.tj + 64 * wc + 32 * sj + (lane & 31);
+            const int cl = 64 * wc + 32 * sj + (lane & 31), lj = kGT * tile.tj + cl;
+            if (lj >= m) continue;
+            const int cj = eTerm[kGT + cl];
 #pragma unroll
             for (int si = 0; si < 2; ++si)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int li = kGT * tile.ti + 64 * wr + 32 * si + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    if (li < m && lj < m)
-                        G16[go + li * gl + lj] = static_cast<uint16_t>(acc[si][sj][r]);
+                    const int rl = 64 * wr + 32 * si + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const int li = kGT * tile.ti + rl;
+                    if (li < m) G16[go + li * gl + lj] = static_cast<uint16_t>(gram_exact(acc[si][sj][r], eTerm[rl], cj));
                 }
         }
         return;
     }
+    if (idle) return;
     // fp64 epilogue (as dbslmm_gram_i8, no-missing form): C/D col = lane & 31,
     // row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const double scale = tau / n_ref_d, rn = 1.0 / n_ref_d;
@@ -553,7 +633,9 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
             for (int r = 0; r < 16; ++r) {
                 const int li = kGT * tile.ti + 64 * wr + 32 * si + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (li >= m) continue;
-                const double c = centre(acc[si][sj][r], S[row0 + li] * Sj, rn);
+                const double Si = S[row0 + li];
+                const double c = centre(static_cast<double>(gram_exact(acc[si][sj][r], gram_row(Si, kpad), gram_col(Sj))),
+                                        Si * Sj, rn);
                 double v = scale * (c * rsd[row0 + li] * rj);
                 if (li == lj) v += 1.0 - tau;
                 for (int cp = copy_lo(m, tmin, tcopy); cp < copy_hi(m, tmin, tcopy, ncopy); ++cp)
@@ -579,18 +661,20 @@ constexpr int kHLdsBytes = 4 * 2 * kHT * (kHK / 4);   // 4 DMA slots x (A | B) x
 constexpr int kKpadAlign = kHK;            // kpad: a multiple of the stage
 }  // namespace gram
 
-// K loop of dbslmm_gram_huge fed by LDS-DMA.  A stage (256 individuals) of a tile row is its 64 B
-// of raw 2-bit Gp codes; global_load_lds_dwordx4 moves them straight into LDS (no staging
+// K loop of dbslmm_gram_huge fed by LDS-DMA.  A stage (256 individuals) of a tile row is 64 B of
+// the raw 2-bit codes of its slot's image row (64-B aligned: the pitch is a multiple of 64);
+// global_load_lds_dwordx4 moves them straight into LDS (no staging
 // registers, no LDS store instructions), four slots (32 KiB each: A | B), three stages in flight.
 // LDS image: row r of an operand at r * 64 B, its 16-B chunk q at position q ^ ((r >> 2) & 3) --
 // the DMA writes lane-linear, so the swizzle goes through the source address -- which puts the
 // 16 rows of every ds_read_b128 lane group on 16 distinct bank groups.  Consumer: lane (row,
 // h = lane >> 5) reads chunk q = 2 j + h of its row (16 B = 64 codes) for k-steps 2 j and 2 j + 1
-// and expands each half (Gp dwords 0-1, 2-3) to one 16-B FP4 operand (fp4_chunk); A and B use the
+// and expands each half (dwords 0-1, 2-3) to one 16-B FP4 operand (raw form: fp4_chunk_raw); A and B use the
 // same individual -> k map, so every product sums each individual once.  NOP = operands staged
 // (1: a diagonal tile, B = A); kFull: every MFMA tile of the wave's piece is active.
 template <int NOP, bool kFull>
-__device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ Gp, int64_t kw,
+__device__ __forceinline__ void gram_huge_dma_loop(const uint8_t* __restrict__ img, int64_t kw,
+                                                   const int32_t* __restrict__ slot_pos, int32_t zrow,
                                                    const int64_t (&rbase)[2], const int (&svl)[2], int nst,
                                                    int8_t* lds, int wave, int lane, int wr, int wc,
                                                    uint32_t act, v16f (&acc)[2][4]) {
@@ -601,6 +685,9 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
     constexpr int kSlotB = 2 * kOpB;                 // A | B
     // DMA map: wave w moves rows 32 w .. 32 w + 31 of each staged operand, 16 rows per
     // instruction; lane L -> row + (L >> 2), LDS position L & 3 holding chunk (L & 3) ^ ((row >> 2) & 3)
+    // The source rows are the image rows of the tile's slots (rows past the valid ones re-read
+    // the last valid slot's row, as before); the slot_pos loads are consumed here, before the
+    // first DMA is issued, so no ordinary load result is awaited while a DMA is in flight.
     const int dr = lane >> 2, dp = lane & 3;
     const uint32_t* gsrc[NOP][2];
 #pragma unroll
@@ -609,7 +696,8 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
         for (int h = 0; h < 2; ++h) {
             const int r = 32 * wave + 16 * h + dr;
             const int q = dp ^ ((r >> 2) & 3);
-            gsrc[op][h] = Gp + (rbase[op] + min(r, svl[op] - 1)) * kw + 4 * q;
+            const int32_t pos = slot_pos[rbase[op] + min(r, svl[op] - 1)];
+            gsrc[op][h] = reinterpret_cast<const uint32_t*>(img) + static_cast<int64_t>(pos < 0 ? zrow : pos) * kw + 4 * q;
         }
     auto issue = [&](int st) {
         int8_t* slot = lds + (st & 3) * kSlotB;
@@ -620,6 +708,7 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
                 __builtin_amdgcn_global_load_lds((gptr_g)(gsrc[op][h] + 16 * st),
                                                  (lptr_g)(slot + op * kOpB + (32 * wave + 16 * h) * kRowB), 16, 0, 0);
     };
+    const uint32_t k44 = raw_k44();              // raw form: acc = T (gram_exact in the epilogues)
     const int rsub = lane & 31, hh = lane >> 5;
     // operand read offsets within a slot (chunk 2 j + hh of the row; j adds 32 B before the swizzle)
     auto roff = [&](int r, int j) { return r * kRowB + 16 * ((2 * j + hh) ^ ((r >> 2) & 3)); };
@@ -637,17 +726,17 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
         auto expand = [&](int j, int e) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                av[i] = fp4_chunk(static_cast<uint32_t>(ar[j][i][2 * e]), static_cast<uint32_t>(ar[j][i][2 * e + 1]));
+                av[i] = fp4_chunk_raw(static_cast<uint32_t>(ar[j][i][2 * e]), static_cast<uint32_t>(ar[j][i][2 * e + 1]), k44);
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj)
-                bv[jj] = fp4_chunk(static_cast<uint32_t>(br[j][jj][2 * e]), static_cast<uint32_t>(br[j][jj][2 * e + 1]));
+                bv[jj] = fp4_chunk_raw(static_cast<uint32_t>(br[j][jj][2 * e]), static_cast<uint32_t>(br[j][jj][2 * e + 1]), k44);
         };
         auto mult = [&]() {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
-                    if (kFull || (act & (1u << (4 * i + jj)))) acc[i][jj] = mfma_fp4(av[i], bv[jj], acc[i][jj]);
+                    if (kFull || (act & (1u << (4 * i + jj)))) acc[i][jj] = mfma_fp4_raw(av[i], bv[jj], acc[i][jj]);
         };
         // k-steps 2 j + e: the reads of j = 1 are issued once k-step 0's operands are expanded, so
         // they land under k-steps 0 and 1's MFMAs (sched_barrier pins that order)
@@ -691,7 +780,8 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
 }
 
 #define GRAM_HUGE_PARAMS                                                                            \
-    const uint32_t* __restrict__ Gp, int64_t kpad,                                                 \
+    const uint8_t* __restrict__ img, int64_t kpad, const int32_t* __restrict__ slot_pos,           \
+    int32_t zrow,                                                                                  \
     const GramTile* __restrict__ tiles, int32_t n_tiles,                                           \
     const int32_t* __restrict__ blk_row0, const int32_t* __restrict__ blk_m,                       \
     const int32_t* __restrict__ blk_ld, const int64_t* __restrict__ blk_matoff,                    \
@@ -700,7 +790,7 @@ __device__ __forceinline__ void gram_huge_dma_loop(const uint32_t* __restrict__ 
     double n_ref_d, double pad_k, double tau, double* __restrict__ M,                              \
     int32_t ncopy, int64_t cstride, int32_t tmin, int32_t tcopy, uint16_t* __restrict__ G16,          \
     const int64_t* __restrict__ g16off, const int32_t* __restrict__ g16ld
-#define GRAM_HUGE_ARGS Gp, kpad, tiles, n_tiles, blk_row0, blk_m, blk_ld, blk_matoff, block_flags, S, \
+#define GRAM_HUGE_ARGS img, kpad, slot_pos, zrow, tiles, n_tiles, blk_row0, blk_m, blk_ld, blk_matoff, block_flags, S, \
     mu, rsd, n_ref_d, pad_k, tau, M, ncopy, cstride, tmin, tcopy, G16, g16off, g16ld
 __device__ __forceinline__ void gram_huge_body(GRAM_HUGE_PARAMS) {
     using namespace gram;
@@ -720,7 +810,7 @@ __device__ __forceinline__ void gram_huge_body(GRAM_HUGE_PARAMS) {
             if (diag && sj > si) continue;
             const int r0 = kHT * tile.ti + 32 * si, c0 = kHT * tile.tj + 32 * sj;
             if (r0 >= m || c0 >= m) continue;
-            gram_tile32(Gp, kpad, row0, m, ld, moff, true, r0, c0, lane, S, mu, rsd, n_ref_d, pad_k,
+            gram_tile32(img, kpad, slot_pos, zrow, row0, m, ld, moff, true, r0, c0, lane, S, mu, rsd, n_ref_d, pad_k,
                         tau, M, ncopy, cstride, tmin, tcopy, nullptr, 0, 0);
         }
         return;
@@ -776,34 +866,17 @@ __device__ __forceinline__ void gram_huge_body(GRAM_HUGE_PARAMS) {
         const int64_t rbase[2] = {row0 + kHT * tile.ti, row0 + kHT * tile.tj};
         const int svl[2] = {rv, cv};
         if (diag) {
-            if (act == 0xFFu) gram_huge_dma_loop<1, true>(Gp, kw, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
-            else gram_huge_dma_loop<1, false>(Gp, kw, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
+            if (act == 0xFFu) gram_huge_dma_loop<1, true>(img, kw, slot_pos, zrow, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
+            else gram_huge_dma_loop<1, false>(img, kw, slot_pos, zrow, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
         } else {
-            if (act == 0xFFu) gram_huge_dma_loop<2, true>(Gp, kw, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
-            else gram_huge_dma_loop<2, false>(Gp, kw, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
+            if (act == 0xFFu) gram_huge_dma_loop<2, true>(img, kw, slot_pos, zrow, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
+            else gram_huge_dma_loop<2, false>(img, kw, slot_pos, zrow, rbase, svl, nst, hlds, wave, lane, wr, wc, act, acc);
         }
     }
-    if (G16) {   // PCG route: the exact integer Gram
-        if (idle) return;
-        const int64_t go = g16off[b], gl = g16ld[b];
-#pragma unroll
-        for (int si = 0; si < 2; ++si)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int li = kHT * tile.ti + 64 * wr + 32 * si + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (li >= m) continue;
-#pragma unroll
-                for (int sj = 0; sj < 4; ++sj) {
-                    const int lj = kHT * tile.tj + 128 * wc + 32 * sj + (lane & 31);
-                    if (!(act & (1u << (4 * si + sj))) || lj >= m) continue;
-                    G16[go + li * gl + lj] = static_cast<uint16_t>(acc[si][sj][r]);
-                }
-            }
-        return;
-    }
-    // fp64 epilogue.  The per-row (S, rsd) and per-column values of the tile go through LDS (the
-    // K loop's last barrier has passed: no wave reads the stages any more), so the element loop
-    // issues no global loads; rows outer, the four column tiles inner.
+    // Epilogues.  The per-row (S, rsd) and per-column values of the tile go through LDS (the
+    // K loop's last barrier has passed: no wave reads the stages any more), so the element loops
+    // issue no global loads; rows outer, the four column tiles inner.  Both need S: the
+    // accumulators hold the raw-form sums T (gram_exact).
     double* eRow = reinterpret_cast<double*>(hlds);   // [S | rsd] of the tile's 256 rows
     double* eCol = eRow + 2 * kHT;                     // [S | rsd] of its 256 columns
     {
@@ -814,6 +887,29 @@ __device__ __forceinline__ void gram_huge_body(GRAM_HUGE_PARAMS) {
     }
     __syncthreads();
     if (idle) return;
+    int cj[4];                                   // gram_exact's column terms
+#pragma unroll
+    for (int sj = 0; sj < 4; ++sj) cj[sj] = gram_col(eCol[128 * wc + 32 * sj + (lane & 31)]);
+    if (G16) {   // PCG route: the exact integer Gram
+        const int64_t go = g16off[b], gl = g16ld[b];
+#pragma unroll
+        for (int si = 0; si < 2; ++si)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rl = 64 * wr + 32 * si + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int li = kHT * tile.ti + rl;
+                if (li >= m) continue;
+                const int ri = gram_row(eRow[rl], kpad);
+#pragma unroll
+                for (int sj = 0; sj < 4; ++sj) {
+                    const int lj = kHT * tile.tj + 128 * wc + 32 * sj + (lane & 31);
+                    if (!(act & (1u << (4 * si + sj))) || lj >= m) continue;
+                    G16[go + li * gl + lj] = static_cast<uint16_t>(gram_exact(acc[si][sj][r], ri, cj[sj]));
+                }
+            }
+        return;
+    }
+    // fp64 epilogue
     const double scale = tau / n_ref_d, rn = 1.0 / n_ref_d;
     double Sj[4], rj[4];
 #pragma unroll
@@ -834,7 +930,8 @@ __device__ __forceinline__ void gram_huge_body(GRAM_HUGE_PARAMS) {
             for (int sj = 0; sj < 4; ++sj) {
                 const int lj = kHT * tile.tj + 128 * wc + 32 * sj + (lane & 31);
                 if (!(act & (1u << (4 * si + sj))) || lj >= m) continue;
-                const double c = centre(acc[si][sj][r], Si * Sj[sj], rn);
+                const double c = centre(static_cast<double>(gram_exact(acc[si][sj][r], gram_row(Si, kpad), cj[sj])),
+                                        Si * Sj[sj], rn);
                 double v = scale * (c * ri * rj[sj]);
                 if (li == lj) v += 1.0 - tau;
                 for (int cp = copy_lo(m, tmin, tcopy); cp < copy_hi(m, tmin, tcopy, ncopy); ++cp)
@@ -851,13 +948,13 @@ extern "C" __global__ __launch_bounds__(512) void dbslmm_gram_huge(GRAM_HUGE_PAR
 // ------------------------------------------------------------------------------------------
 // `valid` (scr/validate.cpp:221-257): deno_b = z1^T (X^T X / n_ref) z1 = |X z1|^2 / n_ref per
 // block, X the nomalizeVec-standardised reference genotypes (missing calls at the mean -> 0).
-// Computed as a weighted row sum straight from the packed .bed (no Gram): thread = one packed
+// Computed as a weighted row sum straight from the packed image rows (no Gram): thread = one packed
 // dword column (16 individuals), looping over the block's SNPs; y = X z1 in fp64 registers; the
 // workgroup reduces sum(y^2) into partial[b][blockIdx.x]; dbslmm_valid_reduce sums the
 // partials of each block in a fixed order (deterministic).
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void dbslmm_valid_partial(
-    const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp,
+    const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
     const int64_t* __restrict__ ptr, const int32_t* __restrict__ pos,
     const double* __restrict__ z1, const double* __restrict__ mu, const double* __restrict__ rsd,
     double* __restrict__ partial, int32_t n_chunks) {
@@ -871,7 +968,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_valid_partial(
     if (w < n_words) {
         const int nv = static_cast<int>(min<int64_t>(16, n_ref - 16 * w));
         for (int64_t j = ptr[b]; j < ptr[b + 1]; ++j) {
-            const uint32_t word = load_u32_any(bed, 3 + static_cast<int64_t>(pos[j]) * bytes_per_snp + 4 * w);
+            const uint32_t word = *reinterpret_cast<const uint32_t*>(img + static_cast<int64_t>(pos[j]) * pitch + 4 * w);
             const double m0 = mu[j], wt = z1[j] * rsd[j];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -921,14 +1018,14 @@ extern "C" __global__ void dbslmm_debug_spin(int64_t ticks) {
 // parity): out[j * n_ref + i] = (g_ij - mu_j) * rsd_j with missing calls at the mean (0).
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void dbslmm_std_columns(
-    const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp,
+    const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
     const int32_t* __restrict__ pos, int32_t n_rows,
     const double* __restrict__ mu, const double* __restrict__ rsd, double* __restrict__ out) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (idx >= static_cast<int64_t>(n_rows) * n_ref) return;
     const int jrow = static_cast<int>(idx / n_ref);
     const int i = static_cast<int>(idx % n_ref);
-    const uint8_t byte = bed[3 + static_cast<int64_t>(pos[jrow]) * bytes_per_snp + (i >> 2)];
+    const uint8_t byte = img[static_cast<int64_t>(pos[jrow]) * pitch + (i >> 2)];
     const int code = (byte >> (2 * (i & 3))) & 3;
     const double g = code == 0 ? 2.0 : code == 2 ? 1.0 : code == 3 ? 0.0 : mu[jrow];
     out[idx] = (g - mu[jrow]) * rsd[jrow];

@@ -2,15 +2,19 @@
 // launches and the extern "C" entry points declared in include/dbslmm_hip.h.
 //
 // HBM layout of a plan (one context = one GPU):
-//   bed       the .bed image as-is (3 magic bytes kept, rows at 3 + r*ceil(n/4)), +16 B pad
+//   image     the resident panel image (dbslmm_bed_repitch, made once per uploaded panel): the
+//             .bed rows without the magic bytes at a pitch of kpad / 4 bytes (64-B aligned rows),
+//             bits past individual n_ref - 1 set (PLINK 11 = dosage 0), one all-0xFF zero-dosage
+//             row at the end; raw PLINK codes in file order, shared by every plan on the panel
 //   slots     non-empty blocks, in block order, each padded to ld = roundup(m + 1, 32) slots:
 //             [small SNPs | large SNPs | padding]; per slot: bed row (-1 = pad), block,
 //             z-score, output index (>= 0 small, -1-i large); slot m of a block doubles as
 //             the row that carries z through the bordered Cholesky
-//   Gp        [n_slots + 256][kpad / 16] dwords of 2-bit dosage codes, kpad = roundup(n_ref, 256)
+//             (kpad = roundup(n_ref, 256); the Gram kernels gather their operand rows from the
+//             image by the slots' bed rows and decode them in registers: no operand buffer)
 //   M         fp64 per block ld x ld row-major, lower triangle; row m = z (written by the solve)
 //   stats     S, mu, 1/sd per slot; y (solve scratch) per slot; flags/status per block
-// The whole problem stays resident; plan_run re-executes unpack -> gram -> chol from the
+// The whole problem stays resident; plan_run re-executes stats -> gram -> chol from the
 // packed genotypes (nothing cached between runs except the uploaded inputs).
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -42,10 +46,10 @@
 #include "pcg.hip"
 
 namespace {
-// events per timed run: [0] start, [1] after unpack, [2] after gram, [3] after chol_large,
+// events per timed run: [0] start, [1] after the statistics pass (slot name: unpack), [2] after gram, [3] after chol_large,
 // [4] / [5] around chol_small (main stream), [6] / [8] around the tiled factorisation sequence,
 // [8] / [7] around the h2f Chebyshev iterations (stream2)
-constexpr int kEvPerRun = 12;   // 9, 10: around the lead group's Gram (between the unpack halves);
+constexpr int kEvPerRun = 12;   // 9, 10: around the lead group's Gram (between the halves of the statistics pass);
                                 // 11: the rest group's factorisation + backward done (its own
                                 // stream, split substitutions; else recorded with 8)
 constexpr size_t kCholLargeLds = sizeof(double) * chol::kLargeDoubles;
@@ -58,7 +62,7 @@ constexpr int kTiledMinDefault = 384;   // blocks with m >= this take the multi-
                                         // 44.1-44.3 -> 43.2-43.3 ms, one run in four 45.0; configs
                                         // 3 / 5 -0.1 / -0.2 ms; 512 before, 320 no better)
 constexpr int kTiledMinSmall = 256;     // the same when no block reaches 512 SNPs (config 2)
-constexpr int kBedPad = 64;            // zero bytes after every device .bed image (the unpack reads whole 16-B chunks)
+constexpr int kBedPad = 64;            // zero bytes after a verbatim .bed upload (dbslmm_bed_repitch reads whole 16-B chunks)
 constexpr int kGramBigMinDefault = 96;  // blocks with m >= this take the 128 x 128 Gram kernel
 constexpr int kGramHugeMinDefault = 384; // ... and the 256 x 256 one from here (swept: configs 3, 5)
 constexpr int kTChebMaxM = 4096;         // whole-block Chebyshev passes: blocks of <= 64 tiles
@@ -88,6 +92,13 @@ constexpr int kGramSq = 4;              // 2D tile squares per XCD of the 256-ti
 constexpr int kTrailSq = 8;             // 2D squares (in 128-tiles) per XCD of the trailing update
 
 int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+// The resident panel image (kernels.hip: dbslmm_bed_repitch): n_rows rows of `pitch` bytes and the
+// zero-dosage row n_rows, made for n_ref individuals.
+struct PanelImage {
+    std::shared_ptr<uint8_t> mem;
+    int64_t pitch = 0;
+    int32_t n_rows = 0, n_ref = 0;
+};
 // Graph capture (launch_graph) vs the device-synchronising setup calls of another host thread
 // (multi-device plans run one thread per shard; several shards may share a device): a
 // hipDeviceSynchronize / synchronous memset or copy while another thread's stream is capturing
@@ -97,7 +108,7 @@ std::mutex g_capture_mu;
 
 struct dbslmm_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;    // main stream (unpack, gram, large-block Cholesky)
+    hipStream_t stream = nullptr;    // main stream (statistics, gram, large-block Cholesky)
     hipStream_t stream2 = nullptr;   // tiled (multi-workgroup) Cholesky sequence, forked/joined
     hipStream_t stream3 = nullptr;   // its bulk trailing updates (lookahead), forked/joined
     // a plan with a lead group (dbslmm_options.lead_min) factors it on stream2 / stream3 and the
@@ -106,13 +117,15 @@ struct dbslmm_ctx {
     hipEvent_t fork = nullptr, join = nullptr, join3 = nullptr, fork2 = nullptr, join4 = nullptr;
     int n_cu = 256;                  // compute units (persistent substitution grid)
     std::string err;
-    // device copy of a caller's .bed image (dbslmm_ctx_cache_bed): bed_maf and plan_create on the
-    // same host range (pointer and length) read it instead of uploading again; a plan created from
-    // it shares the buffer (freed when the context and every such plan have released it)
+    // device copy of a caller's .bed (dbslmm_ctx_cache_bed): bed_maf and plan_create on the same
+    // host range (pointer and length) read it instead of uploading again.  The upload is verbatim
+    // (bed_cache: the cache calls do not know n_ref); the first use that supplies n_ref turns it
+    // into the panel image (img_cache, panel_image()) and releases the verbatim bytes.  A plan
+    // created from it shares the image (freed when the context and every such plan have released it)
     const uint8_t* bed_host = nullptr;
     int64_t bed_host_len = 0;
     std::shared_ptr<uint8_t> bed_cache;
-    uint8_t* d_bed_cache = nullptr;    // bed_cache.get()
+    PanelImage img_cache;
     std::vector<dbslmm_ctx*> subs;   // multi-device context (multi.hip): one context per device,
                                      // device = -1 and no streams of its own
     // dbslmm_ctx_create returns once the main stream exists; the other streams, the events and the
@@ -150,13 +163,12 @@ struct dbslmm_plan {
     dbslmm_mplan* mp = nullptr;        // multi-device plan: every call fans out over its shards
     int32_t n_ref = 0, n_obs = 0, num_block = 0;
     double sigma_s = 0.0, tau = 0.8;
-    int64_t n_s = 0, n_l = 0, bytes_per_snp = 0, kpad = 0, bed_len = 0;
+    int64_t n_s = 0, n_l = 0, kpad = 0, bed_len = 0;
     int32_t n_slots = 0, n_nonempty = 0, n_tiles = 0;
     int64_t M_elems = 0;
     // device
-    uint8_t* d_bed = nullptr;          // own upload, or the context's cached image (bed_shared)
-    std::shared_ptr<uint8_t> bed_shared;
-    uint32_t* d_G = nullptr;   // Gp: 2-bit dosage codes, kpad / 16 dwords per slot
+    PanelImage img;                    // own upload, or the context's cached image (shared)
+    const uint8_t* d_img = nullptr;    // img.mem.get(): pitch kpad / 4, zero-dosage row img.n_rows
     int32_t *d_slot_pos = nullptr, *d_slot_block = nullptr, *d_slot_out = nullptr;
     double *d_z = nullptr, *d_S = nullptr, *d_mu = nullptr, *d_rsd = nullptr, *d_y = nullptr;
     int32_t *d_flags = nullptr, *d_status = nullptr, *d_order = nullptr, *d_blk_id = nullptr;
@@ -175,7 +187,7 @@ struct dbslmm_plan {
     int32_t n_htiles = 0;
     int32_t n_htiles_lead = 0;         // ... of which the first n_htiles_lead are the lead group's,
     int32_t n_htiles_tiled = 0;        //     the first n_htiles_tiled the tiled blocks' (then the rest)
-    int32_t* d_slot_order = nullptr;   // lead group: [its slots | the others'] (unpacked in that order)
+    int32_t* d_slot_order = nullptr;   // lead group: [its slots | the others'] (their statistics run in that order)
     int32_t n_slots_lead = 0;
     bool early_fork = false;           // every tiled block's Gram is in those: the tiled sequences
                                        // may start before the other blocks' Gram
@@ -488,17 +500,70 @@ static void par_memcpy(void* dst, const void* src, size_t n) {
     for (auto& t : th) t.join();
 }
 
-// The .bed image on the device: a device-to-device copy of the context's cached image when the
-// caller passes the same host range, else a staged upload.  dst holds bed_len + kBedPad bytes (zero pad).
+// The verbatim .bed on the device by a staged upload.  dst holds bed_len + kBedPad bytes (zero pad).
 static hipError_t bed_to_device(dbslmm_ctx* ctx, uint8_t* dst, const uint8_t* bed, int64_t bed_len) {
     hipError_t e = hipMemsetAsync(dst + bed_len, 0, kBedPad, ctx->stream);
     if (e != hipSuccess) return e;
-    if (ctx->d_bed_cache && bed == ctx->bed_host && bed_len == ctx->bed_host_len) {
-        e = hipMemcpyAsync(dst, ctx->d_bed_cache, bed_len, hipMemcpyDeviceToDevice, ctx->stream);
-        return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
-    }
     e = hipStreamSynchronize(ctx->stream);
     return e != hipSuccess ? e : upload_staged(dst, bed, bed_len, ctx->stream);
+}
+
+static std::shared_ptr<uint8_t> dev_shared(uint8_t* d, int dev) {
+    return std::shared_ptr<uint8_t>(d, [dev](uint8_t* q) {
+        (void)hipSetDevice(dev);
+        (void)hipFree(q);
+    });
+}
+
+// The panel image of a verbatim device upload d_bed (bed_len + kBedPad bytes) for n_ref
+// individuals; complete on return.
+static hipError_t image_from_verbatim(dbslmm_ctx* ctx, const uint8_t* d_bed, int64_t bed_len, int32_t n_ref,
+                                      PanelImage* out) {
+    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
+    const int64_t n_rows = (bed_len - 3) / bps;
+    if (n_rows >= INT32_MAX) return hipErrorInvalidValue;
+    const int64_t pitch = round_up(n_ref, gram::kKpadAlign) / 4;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc(&d, static_cast<size_t>(n_rows + 1) * pitch);
+    if (e != hipSuccess) return e;
+    PanelImage im;
+    im.mem = dev_shared(d, ctx->device);
+    im.pitch = pitch;
+    im.n_rows = static_cast<int32_t>(n_rows);
+    im.n_ref = n_ref;
+    hipLaunchKernelGGL(dbslmm_bed_repitch, dim3(static_cast<unsigned>((n_rows + 1 + 3) / 4)), dim3(256), 0,
+                       ctx->stream, d_bed, n_ref, bps, im.n_rows, d, pitch);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return e;
+    *out = std::move(im);
+    return hipSuccess;
+}
+
+// The panel image of the host .bed range (bed, bed_len) for n_ref individuals: the context's
+// cached one when the caller passes the cached host range (built from the cached verbatim upload
+// on the first such call, which then releases the verbatim bytes: one resident copy per panel),
+// else an upload of its own.
+static hipError_t panel_image(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
+                              PanelImage* out) {
+    if (bed == ctx->bed_host && bed_len == ctx->bed_host_len) {
+        if (ctx->img_cache.mem && ctx->img_cache.n_ref == n_ref) {
+            *out = ctx->img_cache;
+            return hipSuccess;
+        }
+        if (ctx->bed_cache) {
+            const hipError_t e = image_from_verbatim(ctx, ctx->bed_cache.get(), bed_len, n_ref, &ctx->img_cache);
+            if (e != hipSuccess) return e;
+            ctx->bed_cache.reset();
+            *out = ctx->img_cache;
+            return hipSuccess;
+        }
+        // (cached for another n_ref and the verbatim bytes are gone: upload again below)
+    }
+    uint8_t* d_bed = nullptr;
+    hipError_t e = hipMalloc(&d_bed, bed_len + kBedPad);
+    if (e != hipSuccess) return e;
+    if ((e = bed_to_device(ctx, d_bed, bed, bed_len)) == hipSuccess) e = image_from_verbatim(ctx, d_bed, bed_len, n_ref, out);
+    (void)hipFree(d_bed);
+    return e;
 }
 
 // Allocate and fill a device array on stream st; complete on return.  Every host -> device copy
@@ -801,6 +866,7 @@ void dbslmm_ctx_destroy(dbslmm_ctx* ctx) {
     }
     (void)hipSetDevice(ctx->device);
     ctx->bed_cache.reset();
+    ctx->img_cache = PanelImage{};
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
@@ -821,21 +887,16 @@ int dbslmm_ctx_cache_bed(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len) {
     if (!ctx->subs.empty()) return DBSLMM_OK;   // multi-device: each device gets its own rows
     ARG_CHECK(ctx, (bed == nullptr) == (bed_len == 0) && bed_len >= 0, "bed / bed_len");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->bed_cache.reset();      // plans created from the old image keep their reference
-    ctx->d_bed_cache = nullptr;
+    ctx->bed_cache.reset();
+    ctx->img_cache = PanelImage{};   // plans created from the old image keep their reference
     ctx->bed_host = nullptr;
     ctx->bed_host_len = 0;
     if (!bed) return DBSLMM_OK;
     uint8_t* d = nullptr;
     HIP_TRY(ctx, hipMalloc(&d, bed_len + kBedPad));
-    const int dev = ctx->device;
-    ctx->bed_cache = std::shared_ptr<uint8_t>(d, [dev](uint8_t* q) {
-        (void)hipSetDevice(dev);
-        (void)hipFree(q);
-    });
+    ctx->bed_cache = dev_shared(d, ctx->device);
     HIP_TRY(ctx, hipMemsetAsync(d + bed_len, 0, kBedPad, ctx->stream));
     HIP_TRY(ctx, upload_staged(d, bed, bed_len, ctx->stream));
-    ctx->d_bed_cache = d;
     ctx->bed_host = bed;
     ctx->bed_host_len = bed_len;
     return DBSLMM_OK;
@@ -847,23 +908,18 @@ int dbslmm_ctx_cache_bed_fd(dbslmm_ctx* ctx, int fd, int64_t bed_len, const uint
     ARG_CHECK(ctx, fd >= 0 && key && bed_len > 0, "fd / bed_len / key");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->bed_cache.reset();
-    ctx->d_bed_cache = nullptr;
+    ctx->img_cache = PanelImage{};
     ctx->bed_host = nullptr;
     ctx->bed_host_len = 0;
     uint8_t* d = nullptr;
     HIP_TRY(ctx, hipMalloc(&d, bed_len + kBedPad));
-    const int dev = ctx->device;
-    ctx->bed_cache = std::shared_ptr<uint8_t>(d, [dev](uint8_t* q) {
-        (void)hipSetDevice(dev);
-        (void)hipFree(q);
-    });
+    ctx->bed_cache = dev_shared(d, ctx->device);
     HIP_TRY(ctx, hipMemsetAsync(d + bed_len, 0, kBedPad, ctx->stream));
     if (upload_staged_fd(d, fd, static_cast<size_t>(bed_len), ctx->stream) != hipSuccess) {
         ctx->bed_cache.reset();
         ctx->err = "reading / uploading the .bed from its file descriptor failed";
         return DBSLMM_E_HIP;
     }
-    ctx->d_bed_cache = d;
     ctx->bed_host = key;
     ctx->bed_host_len = bed_len;
     return DBSLMM_OK;
@@ -879,9 +935,8 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
     (void)hipSetDevice(p->ctx->device);
     if (p->h_pin) (void)hipHostFree(p->h_pin);
     if (p->h_pmon) (void)hipHostFree(p->h_pmon);
-    if (p->bed_shared) p->d_bed = nullptr;      // the context's cached image: not ours to free
-    p->bed_shared.reset();
-    void* bufs[] = {p->d_bed, p->d_G, p->d_slot_pos, p->d_slot_block, p->d_slot_out, p->d_z,
+    p->img = PanelImage{};                      // (shared with the context when it came from its cache)
+    void* bufs[] = {p->d_slot_pos, p->d_slot_block, p->d_slot_out, p->d_z,
                     p->d_S, p->d_mu, p->d_rsd, p->d_y, p->d_flags, p->d_status, p->d_order,
                     p->d_blk_id, p->d_row0, p->d_m, p->d_ms, p->d_ld, p->d_matoff, p->d_tiles,
                     p->d_M, p->d_beta_s, p->d_beta_l, p->d_tlist, p->d_btiles, p->d_htiles, p->d_dshift,
@@ -918,8 +973,9 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     *out = nullptr;
     if (const int rc = ctx_ready(ctx)) return rc;
     ARG_CHECK(ctx, pr->bed && pr->n_ref > 1 && pr->n_obs > 0 && pr->num_block >= 0, "bad sizes");
-    // the FP4 Gram accumulates integers up to 4 n_ref in fp32 (exact below 2^24)
-    ARG_CHECK(ctx, pr->n_ref < (1 << 22), "n_ref must be below 4,194,304 (exact FP4 Gram accumulation)");
+    // the FP4 Gram accumulates the raw-form sums, integers up to 9 kpad, in fp32 (exact below 2^24)
+    ARG_CHECK(ctx, 9 * round_up(pr->n_ref, gram::kKpadAlign) < (int64_t(1) << 24),
+              "n_ref must be at most 1,863,936 (exact FP4 Gram accumulation)");
     ARG_CHECK(ctx, pr->s_ptr && (pr->s_ptr[pr->num_block] == 0 || (pr->s_pos && pr->z_s)), "bad small CSR");
     ARG_CHECK(ctx, pr->sigma_s > 0.0 && std::isfinite(pr->sigma_s), "sigma_s must be > 0");
     const int64_t bps = pr->n_ref / 4 + (pr->n_ref % 4 ? 1 : 0);
@@ -935,7 +991,6 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     p->num_block = pr->num_block;
     p->sigma_s = pr->sigma_s;
     p->tau = pr->tau;
-    p->bytes_per_snp = bps;
     p->kpad = round_up(pr->n_ref, gram::kKpadAlign);   // the FP4 Gram's K stage (gram_big: 128 divides it)
     p->bed_len = pr->bed_len;
     const dbslmm_options op = pr->opts ? *pr->opts : dbslmm_options{};
@@ -1180,8 +1235,8 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
             build_tiled(mv, tb_rest, 1, p->n_nonempty, p->tl_rest, tlist);
         }
     }
-    // lead group: its slots are unpacked first, so its Gram (and sequence) need not wait for the
-    // whole unpack
+    // lead group: the statistics of its slots run first, so its Gram (and sequence) need not wait for the
+    // whole pass
     std::vector<int32_t> slot_order;
     if (!p->tl_rest.empty()) {
         std::vector<char> in_lead(p->n_nonempty, 0);
@@ -1286,7 +1341,8 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     const double n_snp = static_cast<double>(p->n_s + p->n_l);
     p->wl[0] = n_snp;
     p->wl[1] = n_snp * bps;
-    p->wl[2] = static_cast<double>(p->n_slots) * (p->kpad / 4);   // Gp bytes the unpack writes
+    // bytes the statistics pass writes: S, mu, 1/sd per slot and the blocks' missing-call flags
+    p->wl[2] = static_cast<double>(p->n_slots) * 3 * sizeof(double) + static_cast<double>(p->n_nonempty) * sizeof(int32_t);
     p->wl[3] = ops_alg;
     p->wl[4] = ops_exec;
     p->wl[5] = chol_flops_large;
@@ -1311,20 +1367,12 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
         return DBSLMM_E_HIP;
     };
     if (e != hipSuccess) return fail("hipSetDevice");
-    if (ctx->d_bed_cache && pr->bed == ctx->bed_host && pr->bed_len == ctx->bed_host_len) {
-        p->bed_shared = ctx->bed_cache;          // read-only: the cached image itself, no copy
-        p->d_bed = p->bed_shared.get();
-    } else {
-        if ((e = hipMalloc(&p->d_bed, pr->bed_len + kBedPad)) != hipSuccess) return fail("hipMalloc bed");
-        if ((e = bed_to_device(ctx, p->d_bed, pr->bed, pr->bed_len)) != hipSuccess) return fail("upload bed");
-    }
-    // + kHT spare rows: a 256-row Gram tile may read past the last slot (results discarded)
-    const int64_t g_bytes = static_cast<int64_t>(p->n_slots + gram::kHT) * (p->kpad / 4);
-    if ((e = hipMalloc(&p->d_G, g_bytes)) != hipSuccess) return fail("hipMalloc G");
+    // the panel image: the context's cached one (read-only, shared: no copy) or an upload of our own
+    if ((e = panel_image(ctx, pr->bed, pr->bed_len, pr->n_ref, &p->img)) != hipSuccess) return fail("upload bed");
+    p->d_img = p->img.mem.get();
     // (every memset of the plan's buffers is ordered on the main stream, which every run starts
     // on: a null-stream hipMemset is not ordered against the context's non-blocking streams, and
     // one still running under the first run's Gram would zero matrix entries behind it)
-    if ((e = hipMemsetAsync(p->d_G, 0, g_bytes, ctx->stream)) != hipSuccess) return fail("hipMemset G");
     if ((e = dev_upload(&p->d_slot_pos, slot_pos, ctx->stream)) != hipSuccess) return fail("upload slots");
     if ((e = dev_upload(&p->d_slot_block, slot_block, ctx->stream)) != hipSuccess) return fail("upload slots");
     if ((e = dev_upload(&p->d_slot_out, slot_out, ctx->stream)) != hipSuccess) return fail("upload slots");
@@ -1396,13 +1444,13 @@ static int collect_timing(dbslmm_plan* p) {
         for (int k = 1; k < kEvPerRun; ++k) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[0], e[k]));
         const float fend = std::max(t[8], t[11]), cstart = std::min(t[8], t[11]);
         float span[DBSLMM_K_COUNT] = {t[1], t[2] - t[1], t[3] - t[2], t[5] - t[4], fend - t[6], t[7] - cstart, 0.f, 0.f};
-        if (r < static_cast<int>(p->run_route.size()) && p->run_route[r]) {   // PCG: unpack, Gram, iterations
+        if (r < static_cast<int>(p->run_route.size()) && p->run_route[r]) {   // PCG: statistics, Gram, iterations
             for (int k = 2; k < DBSLMM_K_COUNT; ++k) span[k] = 0.f;
             span[DBSLMM_K_PCG] = t[7] - t[2];
             span[DBSLMM_K_PCG_BLOCK] = t[4] - t[3];   // (inside the PCG span, on the second stream)
         }
         for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
-        // the lead group's Gram (9 -> 10) sits between the two unpack launches (0 -> 1)
+        // the lead group's Gram (9 -> 10) sits between the two statistics launches (0 -> 1)
         float lg = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&lg, e[9], e[10]));
         p->ms_acc[0] -= lg;
@@ -2232,7 +2280,7 @@ static int pcg_finish(dbslmm_plan* p) {
     return DBSLMM_OK;
 }
 
-// One run on the PCG route: unpack + Gram (the integer Gram as uint16 where it fits, Sigma in fp64
+// One run on the PCG route: statistics + Gram (the integer Gram as uint16 where it fits, Sigma in fp64
 // for the other blocks), then the iterations of every block and copy together.
 static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     dbslmm_ctx* ctx = p->ctx;
@@ -2282,9 +2330,9 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
         hipLaunchKernelGGL(dbslmm_set_scalar, dim3(1), dim3(1), 0, s, p->d_dshift + c,
                            1.0 / (sigmas[c] * static_cast<double>(p->n_obs)));
     if (p->n_slots > 0)
-        hipLaunchKernelGGL(dbslmm_unpack_stats, dim3((p->n_slots + 3) / 4), dim3(256), 0, s, p->d_bed, p->n_ref,
-                           p->bytes_per_snp, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_G, p->kpad, p->d_S,
-                           p->d_mu, p->d_rsd, p->d_flags, nullptr);
+        hipLaunchKernelGGL(dbslmm_snp_stats, dim3((p->n_slots + 3) / 4), dim3(256), 0, s, p->d_img, p->n_ref,
+                           p->img.pitch, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
+                           p->d_flags, nullptr);
     HIP_TRY(ctx, hipGetLastError());
     if (ev) for (int k : {1, 9, 10}) HIP_TRY(ctx, hipEventRecord(ev[k], s));
     uint16_t* g16 = p->pcg_g16 ? p->d_G16 : nullptr;
@@ -2293,15 +2341,18 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     auto gram = [&](hipStream_t st, const GramTile* ti, int32_t nt, const GramTile* tb, int32_t nb,
                     const GramTile* th, int32_t nh) {
         if (nh > 0)
-            hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nh), dim3(512), gram::kHLdsBytes, st, p->d_G, p->kpad, th, nh,
+            hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nh), dim3(512), gram::kHLdsBytes, st, p->d_img, p->kpad,
+                               p->d_slot_pos, p->img.n_rows, th, nh,
                                p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd,
                                padk, p->tau, p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
         if (nt > 0)
-            hipLaunchKernelGGL(dbslmm_gram_i8, dim3((nt + 3) / 4), dim3(256), 0, st, p->d_G, p->kpad, ti, nt, p->d_row0,
+            hipLaunchKernelGGL(dbslmm_gram_i8, dim3((nt + 3) / 4), dim3(256), 0, st, p->d_img, p->kpad, p->d_slot_pos,
+                               p->img.n_rows, ti, nt, p->d_row0,
                                p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd, padk, p->tau,
                                p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
         if (nb > 0)
-            hipLaunchKernelGGL(dbslmm_gram_big, dim3(nb), dim3(256), gram::kLdsBytes, st, p->d_G, p->kpad, tb, nb,
+            hipLaunchKernelGGL(dbslmm_gram_big, dim3(nb), dim3(256), gram::kLdsBytes, st, p->d_img, p->kpad,
+                               p->d_slot_pos, p->img.n_rows, tb, nb,
                                p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd,
                                padk, p->tau, p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
         return hipGetLastError();
@@ -2393,7 +2444,7 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     return DBSLMM_OK;
 }
 
-// One run: unpack + Gram (front; else the Gram of the previous front run is reused), then n
+// One run: statistics + Gram (front; else the Gram of the previous front run is reused), then n
 // factorisations + solves of it, copy c with sigma_s = sigmas[c] (n > 1: h2f tuning; copies
 // 1.. are device copies of the Gram, all factored by one merged tiled sequence).
 static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
@@ -2457,18 +2508,18 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     if (front) HIP_TRY(ctx, hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), s));
     HIP_TRY(ctx, hipMemsetAsync(p->d_status, 0, n * nbk * sizeof(int32_t), s));
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[0], s));
-    auto unpack = [&](const int32_t* list, int32_t n_sl) {
+    auto stats = [&](const int32_t* list, int32_t n_sl) {
         const int wpb = 4;
         dim3 grid((n_sl + wpb - 1) / wpb);
-        hipLaunchKernelGGL(dbslmm_unpack_stats, grid, dim3(256), 0, s, p->d_bed, p->n_ref,
-                           p->bytes_per_snp, p->d_slot_pos, p->d_slot_block, n_sl, p->d_G,
-                           p->kpad, p->d_S, p->d_mu, p->d_rsd, p->d_flags, list);
+        hipLaunchKernelGGL(dbslmm_snp_stats, grid, dim3(256), 0, s, p->d_img, p->n_ref,
+                           p->img.pitch, p->d_slot_pos, p->d_slot_block, n_sl, p->d_S, p->d_mu,
+                           p->d_rsd, p->d_flags, list);
     };
-    // a lead group's slots first: its Gram and sequence start after ~2 % of the unpack
-    const bool split_unpack = front && p->n_slots_lead > 0;
+    // a lead group's slots first: its Gram and sequence start after ~2 % of the pass
+    const bool split_stats = front && p->n_slots_lead > 0;
     if (front && p->n_slots > 0) {
-        if (split_unpack) unpack(p->d_slot_order, p->n_slots_lead);
-        else unpack(nullptr, p->n_slots);
+        if (split_stats) stats(p->d_slot_order, p->n_slots_lead);
+        else stats(nullptr, p->n_slots);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[9], s));
@@ -2492,8 +2543,8 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         }
     }
     auto gram_huge = [&](int32_t t0, int32_t nt) {
-        hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nt), dim3(512), gram::kHLdsBytes, s, p->d_G,
-                           p->kpad, p->d_htiles + t0, nt, p->d_row0, p->d_m, p->d_ld,
+        hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nt), dim3(512), gram::kHLdsBytes, s, p->d_img,
+                           p->kpad, p->d_slot_pos, p->img.n_rows, p->d_htiles + t0, nt, p->d_row0, p->d_m, p->d_ld,
                            p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd,
                            static_cast<double>(p->n_ref), static_cast<double>(p->kpad - p->n_ref),
                            p->tau, p->d_M, n, p->M_elems, tmin_copy, tcopy, nullptr, nullptr, nullptr);
@@ -2510,8 +2561,8 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
         debug_spin(p, s, 1);
     }
-    if (split_unpack) {   // the other slots
-        unpack(p->d_slot_order + p->n_slots_lead, p->n_slots - p->n_slots_lead);
+    if (split_stats) {   // the other slots
+        stats(p->d_slot_order + p->n_slots_lead, p->n_slots - p->n_slots_lead);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));
@@ -2528,8 +2579,8 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     }
     if (front && p->n_tiles > 0) {
         dim3 grid((p->n_tiles + 3) / 4);
-        hipLaunchKernelGGL(dbslmm_gram_i8, grid, dim3(256), 0, s, p->d_G, p->kpad, p->d_tiles,
-                           p->n_tiles, p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S,
+        hipLaunchKernelGGL(dbslmm_gram_i8, grid, dim3(256), 0, s, p->d_img, p->kpad,
+                           p->d_slot_pos, p->img.n_rows, p->d_tiles, p->n_tiles, p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S,
                            p->d_mu, p->d_rsd, static_cast<double>(p->n_ref),
                            static_cast<double>(p->kpad - p->n_ref), p->tau, p->d_M, n, p->M_elems,
                            tmin_copy, tcopy, nullptr, nullptr, nullptr);
@@ -2540,8 +2591,8 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         HIP_TRY(ctx, hipGetLastError());
     }
     if (front && p->n_btiles > 0) {
-        hipLaunchKernelGGL(dbslmm_gram_big, dim3(p->n_btiles), dim3(256), gram::kLdsBytes, s, p->d_G,
-                           p->kpad, p->d_btiles, p->n_btiles, p->d_row0, p->d_m, p->d_ld,
+        hipLaunchKernelGGL(dbslmm_gram_big, dim3(p->n_btiles), dim3(256), gram::kLdsBytes, s, p->d_img,
+                           p->kpad, p->d_slot_pos, p->img.n_rows, p->d_btiles, p->n_btiles, p->d_row0, p->d_m, p->d_ld,
                            p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd,
                            static_cast<double>(p->n_ref), static_cast<double>(p->kpad - p->n_ref),
                            p->tau, p->d_M, n, p->M_elems, tmin_copy, tcopy, nullptr, nullptr, nullptr);
@@ -2792,7 +2843,7 @@ int dbslmm_plan_run(dbslmm_plan* p) {
     return run_impl(p, true, &p->sigma_s, 1);
 }
 
-// h2f tuning (software/DBSLMM.R:204-219 runs dbslmm once per h2 factor): one unpack + Gram, then
+// h2f tuning (software/DBSLMM.R:204-219 runs dbslmm once per h2 factor): one statistics pass + Gram, then
 // n_sigma factorisations + solves of device copies of it, all in one merged launch sequence.
 int dbslmm_plan_run_multi(dbslmm_plan* p, const double* sigmas, int32_t n_sigma, double* beta_s,
                           double* beta_l, int32_t* block_status) {
@@ -3015,9 +3066,9 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
         ARG_CHECK(ctx, o == INT32_MIN || (r >= 0 && r < n_rows), "test SNP bed row out of range");
         tpos[s] = r;
     }
-    const int64_t cbps = (n_test + 3) / 4;
     const int64_t nt_pad = round_up(n_test, 64);
-    const int64_t cbytes = 3 + static_cast<int64_t>(p->n_slots) * cbps + 64;
+    const int64_t cpitch = nt_pad / 4;          // the compacted rows in the panel image's format
+    const int64_t cbytes = std::max<int64_t>(1, p->n_slots) * cpitch;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     uint8_t *d_tbed = nullptr, *d_cbed = nullptr;
@@ -3037,8 +3088,7 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
             (e = upload_staged(d_tbed, tp->bed, tp->bed_len, st)) != hipSuccess ||
             (e = dev_upload(&d_tpos, tpos, ctx->stream)) != hipSuccess || (e = dev_upload(&d_sel, sel, ctx->stream)) != hipSuccess ||
             (e = dev_upload(&d_cpos, cpos, ctx->stream)) != hipSuccess ||
-            (e = hipMalloc(&d_cbed, cbytes)) != hipSuccess ||
-            (e = hipMemsetAsync(d_cbed, 0, cbytes, st)) != hipSuccess ||
+            (e = hipMalloc(&d_cbed, cbytes)) != hipSuccess ||   // (dbslmm_test_compact writes every byte)
             (e = hipMalloc(&d_mu, std::max<int32_t>(1, p->n_slots) * sizeof(double))) != hipSuccess ||
             (e = hipMalloc(&d_rsd, std::max<int32_t>(1, p->n_slots) * sizeof(double))) != hipSuccess ||
             (e = hipMalloc(&d_Y, std::max<int64_t>(1, p->n_slots) * nt_pad * sizeof(double))) != hipSuccess ||
@@ -3049,15 +3099,15 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
             break;
         }
         if (p->n_slots > 0 && p->n_nonempty > 0) {
-            hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cbps + 255) / 256), p->n_slots),
-                               dim3(256), 0, st, d_tbed, tbps, d_tpos, p->n_slots, d_sel, n_test, cbps, d_cbed);
-            hipLaunchKernelGGL(dbslmm_unpack_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
-                               st, d_cbed, n_test, cbps, d_cpos, d_cpos, p->n_slots, nullptr,
-                               nt_pad, nullptr, d_mu, d_rsd, nullptr, nullptr);
+            hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cpitch + 255) / 256), p->n_slots),
+                               dim3(256), 0, st, d_tbed, tbps, d_tpos, p->n_slots, d_sel, n_test, cpitch, d_cbed);
+            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
+                               st, d_cbed, n_test, cpitch, d_cpos, d_cpos, p->n_slots, nullptr, d_mu, d_rsd,
+                               nullptr, nullptr);
             hipLaunchKernelGGL(dbslmm_variance, dim3(static_cast<unsigned>(nt_pad / 64), p->n_nonempty),
                                dim3(256), 0, st, p->d_M + p->var_copy * p->M_elems, p->d_row0, p->d_m,
                                p->d_ms, p->d_ld, p->d_matoff, p->d_blk_id, p->d_status + p->var_copy * p->nbk,
-                               d_cbed, cbps, d_mu, d_rsd, n_test,
+                               d_cbed, cpitch, d_mu, d_rsd, n_test,
                                p->sigma_run, static_cast<double>(p->n_obs), d_Y, nt_pad, d_diags);
         }
         if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess ||
@@ -3082,15 +3132,13 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
     if (n_snp == 0) return DBSLMM_OK;
     if (!ctx->subs.empty()) return mp_bed_maf(ctx, bed, n_ref, n_snp, maf);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* d_bed = nullptr;
+    PanelImage im;            // the context's cached image of this host range, or an upload of our own
     char* d_work = nullptr;   // one allocation: mu | S | maf (doubles), then the per-row missing flags
     int rc = DBSLMM_OK;
     do {
         hipError_t e;
-        const bool cached = ctx->d_bed_cache && bed == ctx->bed_host && bed_len == ctx->bed_host_len;
         const size_t nd = static_cast<size_t>(n_snp) * sizeof(double);
-        if ((!cached && ((e = hipMalloc(&d_bed, bed_len + kBedPad)) != hipSuccess ||
-                         (e = bed_to_device(ctx, d_bed, bed, bed_len)) != hipSuccess)) ||
+        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
             (e = hipMalloc(&d_work, 3 * nd + n_snp * sizeof(int32_t))) != hipSuccess ||
             (e = hipMemsetAsync(d_work + 3 * nd, 0, n_snp * sizeof(int32_t), ctx->stream)) != hipSuccess) {
             ctx->err = std::string("bed_maf alloc/upload: ") + hipGetErrorString(e);
@@ -3101,13 +3149,13 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
         double* d_S = d_mu + n_snp;
         double* d_maf = d_S + n_snp;
         int32_t* d_miss = reinterpret_cast<int32_t*>(d_maf + n_snp);
-        const uint8_t* db = cached ? ctx->d_bed_cache : d_bed;
-        // row k = bed row k (null row lists); per-row missing-call flags (row k's "block" is k)
-        hipLaunchKernelGGL(dbslmm_unpack_stats, dim3(static_cast<unsigned>((n_snp + 3) / 4)), dim3(256), 0,
-                           ctx->stream, db, n_ref, bps, nullptr, nullptr, static_cast<int32_t>(n_snp), nullptr,
-                           round_up(n_ref, 64), d_S, d_mu, nullptr, d_miss, nullptr);
+        const uint8_t* db = im.mem.get();
+        // row k = image row k (null row lists); per-row missing-call flags (row k's "block" is k)
+        hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((n_snp + 3) / 4)), dim3(256), 0,
+                           ctx->stream, db, n_ref, im.pitch, nullptr, nullptr, static_cast<int32_t>(n_snp),
+                           d_S, d_mu, nullptr, d_miss, nullptr);
         hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_snp + 255) / 256)), dim3(256), 0,
-                           ctx->stream, db, n_ref, bps, nullptr, static_cast<int32_t>(n_snp), d_mu, d_maf,
+                           ctx->stream, db, n_ref, im.pitch, nullptr, static_cast<int32_t>(n_snp), d_mu, d_maf,
                            d_S, d_miss);
         if ((e = hipGetLastError()) != hipSuccess ||
             (e = hipMemcpyAsync(maf, d_maf, nd, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
@@ -3116,7 +3164,6 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
             rc = DBSLMM_E_HIP;
         }
     } while (0);
-    (void)hipFree(d_bed);
     (void)hipFree(d_work);
     return rc;
 }
@@ -3132,7 +3179,7 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
         ARG_CHECK(ctx, pos[j] >= 0 && 3 + (pos[j] + 1) * bps <= bed_len, "row out of range");
     if (n_rows == 0) return DBSLMM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t* d_bed = nullptr;
+    PanelImage im;
     int32_t* d_pos = nullptr;
     double *d_mu = nullptr, *d_rsd = nullptr, *d_maf = nullptr, *d_out = nullptr;
     std::vector<int32_t> hp(pos, pos + n_rows);
@@ -3140,9 +3187,7 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
     int rc = DBSLMM_OK;
     do {
         hipError_t e;
-        if ((e = hipMalloc(&d_bed, bed_len + kBedPad)) != hipSuccess ||
-            (e = hipMemsetAsync(d_bed, 0, bed_len + kBedPad, ctx->stream)) != hipSuccess ||
-            (e = upload_staged(d_bed, bed, bed_len, ctx->stream)) != hipSuccess ||
+        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
             (e = dev_upload(&d_pos, hp, ctx->stream)) != hipSuccess ||
             (e = hipMalloc(&d_mu, n_rows * sizeof(double))) != hipSuccess ||
             (e = hipMalloc(&d_rsd, n_rows * sizeof(double))) != hipSuccess ||
@@ -3152,13 +3197,13 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             rc = DBSLMM_E_HIP;
             break;
         }
-        hipLaunchKernelGGL(dbslmm_unpack_stats, dim3((n_rows + 3) / 4), dim3(256), 0, ctx->stream,
-                           d_bed, n_ref, bps, d_pos, d_pos, n_rows, nullptr, round_up(n_ref, 64),
-                           nullptr, d_mu, d_rsd, nullptr, nullptr);
+        const uint8_t* db = im.mem.get();
+        hipLaunchKernelGGL(dbslmm_snp_stats, dim3((n_rows + 3) / 4), dim3(256), 0, ctx->stream,
+                           db, n_ref, im.pitch, d_pos, d_pos, n_rows, nullptr, d_mu, d_rsd, nullptr, nullptr);
         hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
-                           ctx->stream, d_bed, n_ref, bps, d_pos, n_rows, d_mu, d_maf, nullptr, nullptr);
+                           ctx->stream, db, n_ref, im.pitch, d_pos, n_rows, d_mu, d_maf, nullptr, nullptr);
         hipLaunchKernelGGL(dbslmm_std_columns, dim3(static_cast<unsigned>((n_out + 255) / 256)),
-                           dim3(256), 0, ctx->stream, d_bed, n_ref, bps, d_pos, n_rows, d_mu, d_rsd,
+                           dim3(256), 0, ctx->stream, db, n_ref, im.pitch, d_pos, n_rows, d_mu, d_rsd,
                            d_out);
         if ((e = hipGetLastError()) != hipSuccess ||
             (e = hipStreamSynchronize(ctx->stream)) != hipSuccess ||
@@ -3168,7 +3213,6 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             rc = DBSLMM_E_HIP;
         }
     } while (0);
-    (void)hipFree(d_bed);
     (void)hipFree(d_pos);
     (void)hipFree(d_mu);
     (void)hipFree(d_rsd);
@@ -3201,7 +3245,7 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t n_words = (n_ref + 15) / 16;
     const int32_t n_chunks = static_cast<int32_t>((n_words + 255) / 256);
-    uint8_t* d_bed = nullptr;
+    PanelImage im;
     int32_t* d_pos = nullptr;
     int64_t* d_ptr = nullptr;
     double *d_z1 = nullptr, *d_mu = nullptr, *d_rsd = nullptr, *d_part = nullptr, *d_deno = nullptr;
@@ -3212,9 +3256,7 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
     int rc = DBSLMM_OK;
     do {
         hipError_t e;
-        if ((e = hipMalloc(&d_bed, bed_len + kBedPad)) != hipSuccess ||
-            (e = hipMemsetAsync(d_bed, 0, bed_len + kBedPad, ctx->stream)) != hipSuccess ||
-            (e = upload_staged(d_bed, bed, bed_len, ctx->stream)) != hipSuccess ||
+        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
             (e = dev_upload(&d_pos, hp, ctx->stream)) != hipSuccess || (e = dev_upload(&d_ptr, hptr, ctx->stream)) != hipSuccess ||
             (e = dev_upload(&d_z1, hz, ctx->stream)) != hipSuccess ||
             (e = hipMalloc(&d_mu, nr * sizeof(double))) != hipSuccess ||
@@ -3225,12 +3267,13 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             rc = DBSLMM_E_HIP;
             break;
         }
+        const uint8_t* db = im.mem.get();
         if (n_rows > 0)
-            hipLaunchKernelGGL(dbslmm_unpack_stats, dim3(static_cast<unsigned>((n_rows + 3) / 4)), dim3(256), 0,
-                               ctx->stream, d_bed, n_ref, bps, d_pos, d_pos, static_cast<int32_t>(n_rows),
-                               nullptr, round_up(n_ref, 64), nullptr, d_mu, d_rsd, nullptr, nullptr);
+            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((n_rows + 3) / 4)), dim3(256), 0,
+                               ctx->stream, db, n_ref, im.pitch, d_pos, d_pos, static_cast<int32_t>(n_rows),
+                               nullptr, d_mu, d_rsd, nullptr, nullptr);
         hipLaunchKernelGGL(dbslmm_valid_partial, dim3(n_chunks, num_block), dim3(256), 0, ctx->stream,
-                           d_bed, n_ref, bps, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks);
+                           db, n_ref, im.pitch, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks);
         hipLaunchKernelGGL(dbslmm_valid_reduce, dim3((num_block + 255) / 256), dim3(256), 0, ctx->stream,
                            d_part, n_chunks, num_block, static_cast<double>(n_ref), d_deno);
         if ((e = hipGetLastError()) != hipSuccess ||
@@ -3240,7 +3283,7 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             rc = DBSLMM_E_HIP;
         }
     } while (0);
-    void* bufs[] = {d_bed, d_pos, d_ptr, d_z1, d_mu, d_rsd, d_part, d_deno};
+    void* bufs[] = {d_pos, d_ptr, d_z1, d_mu, d_rsd, d_part, d_deno};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
     return rc;

@@ -17,17 +17,19 @@
 // earlier rows (4 waves, 8 rows each, 64 test individuals per workgroup) and a 32-row triangular
 // solve inside the chunk (wave 0, one individual per lane).
 
-// Compact the needed rows of the test .bed to the indicator-1 individuals: out row s (plan slot
-// order) = test row tpos[s] restricted to sel[0..n_test) (-1: padding slot, left as zeros).
+// Compact the needed rows of the test .bed to the indicator-1 individuals, in the panel image's
+// row format (kernels.hip): out row s (plan slot order) at s * cpitch = test row tpos[s] restricted
+// to sel[0..n_test); every code past n_test - 1 up to the pitch, and every code of a padding slot
+// (tpos -1), reads 11 (dosage 0, observed).
 extern "C" __global__ __launch_bounds__(256) void dbslmm_test_compact(
     const uint8_t* __restrict__ tbed, int64_t tbps, const int32_t* __restrict__ tpos,
-    int32_t n_slots, const int32_t* __restrict__ sel, int32_t n_test, int64_t cbps,
+    int32_t n_slots, const int32_t* __restrict__ sel, int32_t n_test, int64_t cpitch,
     uint8_t* __restrict__ out) {
     const int s = blockIdx.y;
     const int64_t q = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (s >= n_slots || q >= cbps) return;
+    if (s >= n_slots || q >= cpitch) return;
     const int32_t row = tpos[s];
-    uint32_t byte = 0;
+    uint32_t byte = 0xFFu;
     if (row >= 0) {
         const uint8_t* src = tbed + 3 + static_cast<int64_t>(row) * tbps;
 #pragma unroll
@@ -35,11 +37,12 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_test_compact(
             const int64_t t = 4 * q + j;
             if (t < n_test) {
                 const int idx = sel[t];
-                byte |= ((static_cast<uint32_t>(src[idx >> 2]) >> (2 * (idx & 3))) & 3u) << (2 * j);
+                const uint32_t code = (static_cast<uint32_t>(src[idx >> 2]) >> (2 * (idx & 3))) & 3u;
+                byte = (byte & ~(3u << (2 * j))) | (code << (2 * j));
             }
         }
     }
-    out[3 + static_cast<int64_t>(s) * cbps + q] = static_cast<uint8_t>(byte);
+    out[static_cast<int64_t>(s) * cpitch + q] = static_cast<uint8_t>(byte);
 }
 
 namespace var {
@@ -47,9 +50,9 @@ constexpr int kRhs = 64;      // test individuals per workgroup
 constexpr int kChunk = 32;    // rows per substitution chunk
 
 // standardised test genotype of slot s for individual t (missing -> the mean -> 0)
-__device__ __forceinline__ double xval(const uint8_t* cbed, int64_t cbps, const double* mu,
+__device__ __forceinline__ double xval(const uint8_t* cbed, int64_t cpitch, const double* mu,
                                        const double* rsd, int s, int t) {
-    const uint32_t code = (static_cast<uint32_t>(cbed[3 + static_cast<int64_t>(s) * cbps + (t >> 2)]) >> (2 * (t & 3))) & 3u;
+    const uint32_t code = (static_cast<uint32_t>(cbed[static_cast<int64_t>(s) * cpitch + (t >> 2)]) >> (2 * (t & 3))) & 3u;
     if (code == 1u) return 0.0;
     const double g = code == 0 ? 2.0 : (code == 2 ? 1.0 : 0.0);
     return (g - mu[s]) * rsd[s];
@@ -61,7 +64,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_variance(
     const int32_t* __restrict__ blk_m, const int32_t* __restrict__ blk_ms,
     const int32_t* __restrict__ blk_ld, const int64_t* __restrict__ blk_matoff,
     const int32_t* __restrict__ blk_id, const int32_t* __restrict__ status,
-    const uint8_t* __restrict__ cbed, int64_t cbps, const double* __restrict__ mu,
+    const uint8_t* __restrict__ cbed, int64_t cpitch, const double* __restrict__ mu,
     const double* __restrict__ rsd, int32_t n_test, double sigma_s, double n_obs,
     double* __restrict__ Y, int64_t nt_pad, double* __restrict__ diags) {
     using namespace var;
@@ -83,7 +86,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_variance(
             const int r = i0 + 8 * g + u;
             double x = 0.0;
             if (act && r < ms) {
-                x = var::xval(cbed, cbps, mu, rsd, row0 + r, t);
+                x = var::xval(cbed, cpitch, mu, rsd, row0 + r, t);
                 xs2 += x * x;
             }
             a8[u] = x;
@@ -122,7 +125,7 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_variance(
     // pass 2 (blocks with large SNPs): y' = L^-1 [0; x_l], rows ms .. m-1 only (wave 0)
     if (g == 0 && m > ms) {
         for (int r = ms; r < m; ++r) {
-            double a = act ? var::xval(cbed, cbps, mu, rsd, row0 + r, t) : 0.0;
+            double a = act ? var::xval(cbed, cpitch, mu, rsd, row0 + r, t) : 0.0;
             for (int k = ms; k < r; ++k) a -= A[static_cast<int64_t>(r) * ld + k] * (act ? Yb[static_cast<int64_t>(k) * nt_pad] : 0.0);
             const double y = a * A[static_cast<int64_t>(r) * ld + r];
             if (act) Yb[static_cast<int64_t>(r) * nt_pad] = y;

@@ -199,9 +199,11 @@ typedef struct dbslmm_problem {
 
 /* Kernel timing slots reported by dbslmm_plan_kernel_ms. */
 enum {
-    DBSLMM_K_UNPACK = 0,      /* dbslmm_unpack_stats: 2-bit .bed rows -> 2-bit dosage codes + stats */
+    DBSLMM_K_UNPACK = 0,      /* dbslmm_snp_stats: per-SNP statistics of the slots' 2-bit panel rows
+                                 (the slot keeps the name of the unpack that used to run here) */
     DBSLMM_K_GRAM = 1,        /* dbslmm_gram_i8 / _big / _huge: FP4-MFMA grouped syrk of the exact
-                                 integer dosages (2-bit codes expanded on the fly) + fp64
+                                 integer dosages (raw 2-bit panel rows gathered, decoded and
+                                 expanded on the fly) + fp64
                                  standardising epilogue (PCG route: the integer Gram as uint16) */
     DBSLMM_K_CHOL_LARGE = 2,  /* dbslmm_chol_large: blocks with 64 <= m+1 and m below the tiled
                                  threshold, one workgroup each */
@@ -282,9 +284,11 @@ const char* dbslmm_last_error(const dbslmm_ctx* ctx);
  * MAF pass (IO::readBim, dtpr.cpp:93-102) and again per block in calcBlock (dbslmmfit.cpp:
  * 384-387).  The cached image is matched by host pointer and length only: the caller must not
  * modify the buffer, or free it and pass a new one at the same address, while it is cached
- * (call this again, or with bed == NULL, after any change).  A plan created from the cached image
- * reads it in place (no second device copy) and keeps it alive until the plan is destroyed, even
- * if the context releases or replaces it.  bed == NULL releases the context's reference.  A
+ * (call this again, or with bed == NULL, after any change).  The upload is kept verbatim until the
+ * first call that supplies n_ref, which turns it into the row-aligned panel image the kernels read
+ * (one resident copy either way; a later call with another n_ref uploads for itself).  A plan
+ * created from the cached image reads it in place (no second device copy) and keeps it alive until
+ * the plan is destroyed, even if the context releases or replaces it.  bed == NULL releases the context's reference.  A
  * multi-device context ignores the call (each device holds only its shard's rows). */
 int dbslmm_ctx_cache_bed(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len);
 /* dbslmm_ctx_cache_bed with the image read from an open file descriptor (pread straight into the
@@ -325,8 +329,8 @@ void dbslmm_plan_destroy(dbslmm_plan* plan);
 int dbslmm_plan_enable_timing(dbslmm_plan* plan, int enable);
 int dbslmm_plan_kernel_ms(dbslmm_plan* plan, double* ms_out /*[DBSLMM_K_COUNT]*/, int32_t* launches_out);
 
-/* Workload figures of the plan (for rooflines): [0] SNPs, [1] packed bytes read by the unpack,
- * [2] Gram operand (2-bit dosage code) bytes written by the unpack, [3] Gram ops (2 per MAC, algorithmic
+/* Workload figures of the plan (for rooflines): [0] SNPs, [1] packed bytes read by the statistics
+ * pass, [2] bytes it writes (S, mean, 1/sd per slot and the blocks' missing-call flags), [3] Gram ops (2 per MAC, algorithmic
  * sum_b n_ref*m_b*(m_b+1)), [4] Gram ops as executed on padded tiles, [5] Cholesky+solve fp64
  * flops of the large blocks (sum_b m_b^3/3 + 2 m_b^2), [6] non-empty blocks, [7] gram tiles,
  * [8] the same fp64 flops for the small blocks, [9] large blocks, [10] the same fp64 flops for

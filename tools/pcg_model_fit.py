@@ -56,9 +56,11 @@ def main(cal, prof=None):
         gb = per_run.get("dbslmm_gram_big", 0) + per_run.get("dbslmm_gram_i8", 0)
         print(f"  gram huge {gh:8.1f} us -> {ops[m >= hm].sum() / gh * 1e-9 * 1e3 / 1e3:.3f} Pops/s;"
               f" big {gb:8.1f} us -> {ops[m < hm].sum() / max(gb, 1e-9) * 1e-9:.3f} Pops/s")
-        up = per_run.get("dbslmm_unpack_stats", 0)
-        ub = m.sum() * (math.ceil(n_ref / 4) + kp / 4)
-        print(f"  unpack {up:8.1f} us -> {ub / up * 1e-6:.2f} TB/s")
+        if "dbslmm_snp_stats" in per_run:               # the statistics pass reads the image rows
+            up, ub = per_run["dbslmm_snp_stats"], m.sum() * math.ceil(n_ref / 256) * 64
+        else:                                           # traces up to round 6: the unpack also wrote Gp
+            up, ub = per_run.get("dbslmm_unpack_stats", 0), m.sum() * (math.ceil(n_ref / 4) + kp / 4)
+        print(f"  stats / unpack {up:8.1f} us -> {ub / up * 1e-6:.2f} TB/s")
         oth = sum(v for n, v in per_run.items() if "rocclr" in n or n in ("dbslmm_pcg_init", "dbslmm_pcg_final",
                                                                           "dbslmm_set_scalar"))
         print(f"  other (copies, fills, init, final) {oth:8.1f} us/run; step {r['step_ms']:.3f} ms")

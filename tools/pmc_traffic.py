@@ -37,7 +37,7 @@ def main(src, dst, bench_args=""):
            "kernels": {}}
     # runs: one dbslmm_pcg_init per run on the PCG route, else one dbslmm_gram_i8
     runs = f.get("dbslmm_pcg_init", (0, 0))[1] or f.get("dbslmm_gram_i8", (0, 0))[1]
-    seq = trsv = gram = pcg = 0.0
+    seq = trsv = gram = pcg = stats = 0.0
     for k in sorted(set(f) | set(w)):
         name = k[5:] if k.startswith("void ") else k
         if not name.startswith("dbslmm_"):
@@ -48,6 +48,8 @@ def main(src, dst, bench_args=""):
             seq += (2 * fk + wk) * 1024.0 * n
         elif name.startswith("dbslmm_trsv_"):
             trsv += (2 * fk + wk) * 1024.0 * n
+        if name == "dbslmm_snp_stats":
+            stats += (2 * fk + wk) * 1024.0 * n
         if name.startswith("dbslmm_gram_"):
             gram += (2 * fk + wk) * 1024.0 * n
         elif name.startswith("dbslmm_pcg_") and name != "dbslmm_pcg_block":
@@ -58,6 +60,9 @@ def main(src, dst, bench_args=""):
     if runs and trsv:
         out["kernels"]["dbslmm_trsv"] = dict(hbm_bytes_per_step=trsv / runs, runs=runs,
                                              note="h2f substitutions (CG by default), per run")
+    if runs and stats:   # the bench's timing slot of the statistics pass keeps the unpack's name
+        out["kernels"]["dbslmm_unpack_stats"] = dict(hbm_bytes_per_step=stats / runs, runs=runs,
+                                                     note="dbslmm_snp_stats launches, per run")
     if runs and gram:
         out["kernels"]["dbslmm_gram"] = dict(hbm_bytes_per_step=gram / runs, runs=runs,
                                              note="dbslmm_gram_huge / _big / _i8 launches, per run")
