@@ -126,6 +126,7 @@ struct dbslmm_ctx {
     int64_t bed_host_len = 0;
     std::shared_ptr<uint8_t> bed_cache;
     PanelImage img_cache;
+    bool bed_from_fd = false;        // cached by dbslmm_ctx_cache_bed_fd: bed_host is a key, never read
     std::vector<dbslmm_ctx*> subs;   // multi-device context (multi.hip): one context per device,
                                      // device = -1 and no streams of its own
     // dbslmm_ctx_create returns once the main stream exists; the other streams, the events and the
@@ -333,6 +334,22 @@ struct dbslmm_plan {
             (ctx)->err = msg;                       \
             return DBSLMM_E_ARG;                    \
         }                                           \
+    } while (0)
+
+// An image cached from a file descriptor has no host bytes behind its key: once the verbatim
+// upload has become the panel image of one n_ref, a call that passes the key with another n_ref
+// cannot be served (the host-array cache uploads again from its pointer, panel_image()).
+static bool key_of_other_n_ref(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref) {
+    if (!ctx->bed_from_fd || bed != ctx->bed_host || bed_len != ctx->bed_host_len || ctx->bed_cache ||
+        !ctx->img_cache.mem || ctx->img_cache.n_ref == n_ref)
+        return false;
+    ctx->err = "the image cached from a file descriptor was built for n_ref = " +
+               std::to_string(ctx->img_cache.n_ref) + "; cache it again to use n_ref = " + std::to_string(n_ref);
+    return true;
+}
+#define KEY_CHECK(ctx, bed, bed_len, nref)                                              \
+    do {                                                                                \
+        if (key_of_other_n_ref(ctx, bed, bed_len, nref)) return DBSLMM_E_STATE;         \
     } while (0)
 
 // multi-device plans (multi.hip)
@@ -556,7 +573,8 @@ static hipError_t panel_image(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_l
             *out = ctx->img_cache;
             return hipSuccess;
         }
-        // (cached for another n_ref and the verbatim bytes are gone: upload again below)
+        // (cached for another n_ref and the verbatim bytes are gone: upload again below -- a host
+        // array; the entry points turn a file-descriptor key away before this, KEY_CHECK)
     }
     uint8_t* d_bed = nullptr;
     hipError_t e = hipMalloc(&d_bed, bed_len + kBedPad);
@@ -891,6 +909,7 @@ int dbslmm_ctx_cache_bed(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len) {
     ctx->img_cache = PanelImage{};   // plans created from the old image keep their reference
     ctx->bed_host = nullptr;
     ctx->bed_host_len = 0;
+    ctx->bed_from_fd = false;
     if (!bed) return DBSLMM_OK;
     uint8_t* d = nullptr;
     HIP_TRY(ctx, hipMalloc(&d, bed_len + kBedPad));
@@ -911,6 +930,7 @@ int dbslmm_ctx_cache_bed_fd(dbslmm_ctx* ctx, int fd, int64_t bed_len, const uint
     ctx->img_cache = PanelImage{};
     ctx->bed_host = nullptr;
     ctx->bed_host_len = 0;
+    ctx->bed_from_fd = false;
     uint8_t* d = nullptr;
     HIP_TRY(ctx, hipMalloc(&d, bed_len + kBedPad));
     ctx->bed_cache = dev_shared(d, ctx->device);
@@ -922,6 +942,7 @@ int dbslmm_ctx_cache_bed_fd(dbslmm_ctx* ctx, int fd, int64_t bed_len, const uint
     }
     ctx->bed_host = key;
     ctx->bed_host_len = bed_len;
+    ctx->bed_from_fd = true;
     return DBSLMM_OK;
 }
 
@@ -981,6 +1002,7 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     const int64_t bps = pr->n_ref / 4 + (pr->n_ref % 4 ? 1 : 0);
     const int64_t n_snp_bed = (pr->bed_len - 3) / bps;
     ARG_CHECK(ctx, pr->bed_len >= 3 + bps, "bed image shorter than one SNP row");
+    KEY_CHECK(ctx, pr->bed, pr->bed_len, pr->n_ref);
     const bool has_l = pr->l_ptr != nullptr;
     if (has_l) ARG_CHECK(ctx, pr->l_ptr[pr->num_block] == 0 || (pr->l_pos && pr->z_l), "bad large CSR");
 
@@ -3131,6 +3153,7 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
     ARG_CHECK(ctx, bed_len >= 3 + n_snp * bps, "bed image shorter than n_snp rows");
     if (n_snp == 0) return DBSLMM_OK;
     if (!ctx->subs.empty()) return mp_bed_maf(ctx, bed, n_ref, n_snp, maf);
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PanelImage im;            // the context's cached image of this host range, or an upload of our own
     char* d_work = nullptr;   // one allocation: mu | S | maf (doubles), then the per-row missing flags
@@ -3178,6 +3201,7 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
     for (int32_t j = 0; j < n_rows; ++j)
         ARG_CHECK(ctx, pos[j] >= 0 && 3 + (pos[j] + 1) * bps <= bed_len, "row out of range");
     if (n_rows == 0) return DBSLMM_OK;
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PanelImage im;
     int32_t* d_pos = nullptr;
@@ -3242,6 +3266,7 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
         nume[b] = t;
     }
     if (num_block == 0) return DBSLMM_OK;
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int64_t n_words = (n_ref + 15) / 16;
     const int32_t n_chunks = static_cast<int32_t>((n_words + 255) / 256);

@@ -296,7 +296,11 @@ int dbslmm_ctx_cache_bed(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len);
  * the file pays no page faults and no page-table teardown for it).  `key` -- typically the
  * caller's mmap of the same file, never dereferenced here -- identifies the image: dbslmm_bed_maf
  * and dbslmm_plan_create calls that pass (key, bed_len) as their .bed read the cached copy.  The
- * file must not change while cached.  (ABI 8; the dbslmm CLI uses it.) */
+ * cached copy serves ONE n_ref, that of the first such call (which turns the verbatim bytes into
+ * the panel image and releases them): a later call that passes (key, bed_len) with another n_ref
+ * returns DBSLMM_E_STATE -- dbslmm_last_error names the cached n_ref -- and does not read through
+ * key; call this again (or dbslmm_ctx_cache_bed) to use the other n_ref.  The file must not change
+ * while cached.  (ABI 8; the dbslmm CLI uses it.) */
 int dbslmm_ctx_cache_bed_fd(dbslmm_ctx* ctx, int fd, int64_t bed_len, const uint8_t* key);
 
 /* DBSLMMFIT::est replacement: upload, solve, download, free.  beta_s has s_ptr[num_block]
