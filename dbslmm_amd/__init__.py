@@ -8,6 +8,8 @@ entry points mirror the reference operator interface (fboehm/DBSLMM, scr/dbslmmf
 * ``Plan``                -- the same problem kept resident in HBM for repeated solves.
 * ``bed_maf``             -- the MAF pass of IO::readBim (dtpr.cpp:93-102).
 * ``read_snp_std``        -- IO::readSNPIm + SNPPROC::nomalizeVec for a list of rows.
+* ``Context.row_stats``   -- the exact per-row integers (sum, sum of squares, missing calls) the
+  resident panel image keeps and every per-row statistic derives from (tests, diagnostics).
 
 All compute runs on the GPU through the HIP library; there is no CPU fallback.
 """
@@ -64,6 +66,15 @@ class Context:
         b = np.ascontiguousarray(bed, dtype=np.uint8)
         self.check(self.lib.dbslmm_ctx_cache_bed(self.h, _ptr(b), b.size), "ctx_cache_bed")
         self._cached_bed = b       # the host range must stay alive and unchanged
+
+    def row_stats(self, bed, n_ref: int, n_rows: int) -> np.ndarray:
+        """The panel image's row table (dbslmm_bed_row_stats): an (n_rows, 3) int32 array of the
+        exact per-row dosage sum, sum of squares and missing-call count."""
+        b = np.ascontiguousarray(bed, dtype=np.uint8)
+        out = np.zeros((n_rows, 3), dtype=np.int32)
+        self.check(self.lib.dbslmm_bed_row_stats(self.h, _ptr(b), b.size, n_ref, n_rows, _ptr(out)),
+                   "bed_row_stats")
+        return out
 
     def check(self, rc: int, what: str):
         if rc != 0:

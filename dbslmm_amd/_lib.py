@@ -21,10 +21,10 @@ EXPORTS = (
     "dbslmm_ctx_create_multi", "dbslmm_ctx_num_devices", "dbslmm_plan_shard_info",
     "dbslmm_ctx_cache_bed", "dbslmm_ctx_cache_bed_fd", "dbslmm_plan_block_matrix",
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
-    "dbslmm_plan_block_iters",
+    "dbslmm_plan_block_iters", "dbslmm_bed_row_stats",
 )
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
@@ -103,6 +103,7 @@ def load(path: str | None = None):
     L.dbslmm_plan_kernel_ms.argtypes = [V, V, V]
     L.dbslmm_plan_workload.argtypes = [V, V]
     L.dbslmm_bed_maf.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int64, V]
+    L.dbslmm_bed_row_stats.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int64, V]
     L.dbslmm_read_snp_std.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V, V]
     L.dbslmm_valid_blocks.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V, V, V]
     L.dbslmm_plan_variance.argtypes = [V, P(TestPanel), V, V]

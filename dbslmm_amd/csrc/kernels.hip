@@ -7,10 +7,14 @@
 //                        bytes (a multiple of 64), every bit past individual n_ref - 1 set
 //                        (PLINK code 11 = dosage 0), plus one all-0xFF zero-dosage row at the
 //                        end.  Raw PLINK codes in file row order: no slot order, no decode.
-//   dbslmm_snp_stats     IO::readSNPIm + nomalizeVec statistics (scr/dtpr.cpp:285-380): exact
-//                        integer per-SNP count / sum / sum-of-squares (popcounts) of the image
-//                        rows of the plan's slots and the fp64 mean and 1/sd (N-1).  HBM-bound
-//                        (read only), one wave per slot.
+//                        The same pass leaves the ROW TABLE behind the image: per row the exact
+//                        integers {dosage sum, sum of squares, missing calls} (popcounts of the
+//                        words it writes), the only thing the statistics of a row depend on.
+//   dbslmm_slot_stats    IO::readSNPIm + nomalizeVec statistics (scr/dtpr.cpp:285-380) of the
+//                        plan's slots: a gather from the row table, one thread per slot -- the
+//                        fp64 mean and 1/sd (N-1) from the exact integer count / sum / sum of
+//                        squares.  (dbslmm_snp_stats: the same from the rows themselves, one
+//                        wave per row, for panels that are no image -- the variance path.)
 //   dbslmm_gram_i8 /     estBlock's LD matrices (scr/dbslmmfit.cpp:697-709, 751-756) as ONE
 //   dbslmm_gram_big /    joint Gram per block over [small | large] SNPs on the FP4 matrix cores
 //   dbslmm_gram_huge     (v_mfma_scale_f32_32x32x64_f8f6f4, exact integer sums in fp32; the
@@ -107,7 +111,7 @@ __device__ __forceinline__ v16f mfma_fp4(v4i a, v4i b, v16f c) {
 // exact in fp32 -- and the epilogues recover the same exact integer Gram before anything else
 // uses it (gram_exact, in int32: a row term 3 S_a - 9 kpad and a column term 3 S_b formed once
 // per row / column, one conversion and one add3 per element):
-//     G_ab = T_ab - 9 kpad + 3 (S_a + S_b),  S the integer dosage sums of dbslmm_snp_stats.
+//     G_ab = T_ab - 9 kpad + 3 (S_a + S_b),  S the integer dosage sums of dbslmm_slot_stats.
 // k44 = 0x44444444 is held in a VGPR (gfx9 VOP3 takes one scalar operand and no literal): one
 // v_and_or_b32 per FP4 dword, no more VALU than the decoded form's plain mask.
 constexpr int kE8M0Half = 0x7E7E7E7E;                      // E8M0 scale 2^-1 in every byte
@@ -157,6 +161,9 @@ __device__ __forceinline__ void split_missing(uint32_t w, uint32_t& g, uint32_t&
 // allocated bytes, so the last row's loads stay inside the allocation.  Bits past individual
 // n_ref - 1 (the pad bits of the last data byte and every byte up to the pitch) are set: PLINK
 // code 11 = dosage 0, observed -- whatever the file holds there.
+// The wave also reduces the row's exact integers {sum, sumsq, nmiss} over the masked words it
+// writes (count_word) and lane 0 stores them as entry r of the row table tab (16 B per row, the
+// zero-dosage row's entry all zero): every later reader of per-row statistics gathers from it.
 // ------------------------------------------------------------------------------------------
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u4v load_u4(const uint8_t* p) { return *reinterpret_cast<const u4v*>(p); }
@@ -176,9 +183,34 @@ __device__ __forceinline__ u4v shift_pair(u4v x, u4v y, int d, int bs) {
     return r;
 }
 
+// exact integer statistics of one raw image dword (16 PLINK codes; 11 = dosage 0, so set pad bits
+// count for nothing)
+__device__ __forceinline__ void count_word(uint32_t word, int& sum, int& sq, int& nmiss) {
+    const uint32_t lo2 = word & 0x55555555u;
+    const uint32_t hi2 = (word >> 1) & 0x55555555u;
+    const int n_miss = __builtin_popcount(lo2 & ~hi2);
+    const int n_two = __builtin_popcount(~lo2 & ~hi2 & 0x55555555u);
+    const int n_one = __builtin_popcount(~lo2 & hi2);
+    nmiss += n_miss;
+    sum += 2 * n_two + n_one;
+    sq += 4 * n_two + n_one;
+}
+// mean over observed calls (the imputation value), 1/sd (N-1 divisor; +inf when monomorphic) and
+// the observed dosage sum of a row from its exact integers -- ONE sequence of fp64 operations for
+// every producer of these values (results are compared bit for bit)
+__device__ __forceinline__ void row_moments(int32_t n_ref, int sum, int sq, int nmiss, double& ds, double& mu,
+                                            double& rsd) {
+    const double dc = static_cast<double>(n_ref - nmiss);       // observed calls
+    ds = static_cast<double>(sum);
+    mu = ds / dc;                                                // imputation value
+    const double css = static_cast<double>(sq) - ds * ds / dc;  // centred sum of squares
+    const double sd = sqrt(css / static_cast<double>(n_ref - 1));
+    rsd = 1.0 / sd;
+}
+
 extern "C" __global__ __launch_bounds__(256) void dbslmm_bed_repitch(
     const uint8_t* __restrict__ bed, int32_t n_ref, int64_t bytes_per_snp, int32_t n_rows,
-    uint8_t* __restrict__ img, int64_t pitch) {
+    uint8_t* __restrict__ img, int64_t pitch, v4i* __restrict__ tab) {
     const int lane = threadIdx.x & (kWave - 1);
     const int r = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     if (r > n_rows) return;
@@ -186,12 +218,14 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_bed_repitch(
     const int nq = static_cast<int>(pitch / 16);           // 16-B chunks of the image row
     if (r == n_rows) {                                      // the zero-dosage row
         for (int q = lane; q < nq; q += kWave) out[q] = u4v{~0u, ~0u, ~0u, ~0u};
+        if (lane == 0) tab[r] = v4i{0, 0, 0, 0};
         return;
     }
     const int64_t row_off = 3 + static_cast<int64_t>(r) * bytes_per_snp;
     const uint8_t* base = bed + (row_off & ~int64_t(15));
     const int sh = static_cast<int>(row_off & 15), dsh = sh >> 2, bsh = sh & 3;
     const int nqd = (n_ref + 63) / 64;          // chunks holding individuals
+    int sum = 0, sq = 0, nmiss = 0;             // of the words written (pad bits set: they count for nothing)
     for (int q = lane; q < nq; q += kWave) {
         u4v g = u4v{~0u, ~0u, ~0u, ~0u};
         if (q < nqd) {
@@ -202,40 +236,67 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_bed_repitch(
                 const int nv = min(16, max(0, n_ref - (64 * q + 16 * j)));
                 const uint32_t keep = nv >= 16 ? ~0u : (1u << (2 * nv)) - 1u;
                 g[j] = wv[j] | ~keep;
+                count_word(g[j], sum, sq, nmiss);
             }
         }
         out[q] = g;
     }
+    sum = wave_sum_i32(sum);
+    sq = wave_sum_i32(sq);
+    nmiss = wave_sum_i32(nmiss);
+    if (lane == 0) tab[r] = v4i{sum, sq, nmiss, 0};
 }
 
 // ------------------------------------------------------------------------------------------
-// Kernel 1: per-SNP statistics of image rows.  One wave per slot (SNP row of a block), 4 waves/WG.
+// Kernel 1: per-slot statistics from the row table.  One thread per slot (SNP row of a block).
 //   mu, rsd, S     fp64: mean over observed calls (= the imputation value, dtpr.cpp:358),
 //                  1/sd with the N-1 divisor (nomalizeVec), sum of observed dosages -- from the
-//                  exact integer count / sum / sum of squares over the n_ref individuals.
+//                  row's exact integer sum / sum of squares / missing count (row_moments).
 //   block_flags    bit 0 set when a slot of the block has a missing call.
-//   slot_list      optional: only these n_slots slots (the plan takes its lead group first)
-// Image rows are 64-B aligned and their bits past n_ref read 11 (neither missing nor a dosage),
-// so lane q of a pass takes the row's 16-B chunk q (64 individuals) with one dwordx4 load, kU
-// chunks per lane in flight, and no popcount needs a tail mask.  Nothing but the statistics is
-// written: the Gram kernels read the image rows themselves.
+//   slot_pos       image row of each slot (< 0: padding slot, zeros); null: slot k = row k.
+//   slot_block     flag index of each slot; null: the slot itself (per-row missing indicator).
+// ------------------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256) void dbslmm_slot_stats(
+    const v4i* __restrict__ tab, int32_t n_ref,
+    const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
+    double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
+    int32_t* __restrict__ block_flags) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_slots) return;
+    const int32_t pos = slot_pos ? slot_pos[slot] : slot;
+    double ds = 0.0, mu = 0.0, rsd = 0.0;       // padding slot
+    int nmiss = 0;
+    if (pos >= 0) {
+        const v4i e = tab[pos];
+        nmiss = e[2];
+        row_moments(n_ref, e[0], e[1], nmiss, ds, mu, rsd);
+    }
+    if (S_out) S_out[slot] = ds;
+    if (mu_out) mu_out[slot] = mu;
+    if (rsd_out) rsd_out[slot] = rsd;
+    if (nmiss > 0 && block_flags) atomicOr(block_flags + (slot_block ? slot_block[slot] : slot), 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same statistics from the rows themselves, for 2-bit rows that are no panel image with a row
+// table (the variance path's compacted test panel).  One wave per slot, 4 waves/WG.
+// Rows are 64-B aligned and their bits past n_ref read 11 (neither missing nor a dosage), so lane
+// q of a pass takes the row's 16-B chunk q (64 individuals) with one dwordx4 load, kU chunks per
+// lane in flight, and no popcount needs a tail mask.  Nothing but the statistics is written.
 // ------------------------------------------------------------------------------------------
 extern "C" __global__ __launch_bounds__(256) void dbslmm_snp_stats(
     const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
-    const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
-    double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
-    int32_t* __restrict__ block_flags, const int32_t* __restrict__ slot_list) {
+    const int32_t* __restrict__ slot_pos, int32_t n_slots,
+    double* __restrict__ mu_out, double* __restrict__ rsd_out) {
     constexpr int kU = 4;                       // chunks per lane per pass (loads in flight)
     const int lane = threadIdx.x & (kWave - 1);
-    const int k = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-    if (k >= n_slots) return;
-    const int slot = slot_list ? slot_list[k] : k;   // a subset of the slots (n_slots of them)
-    const int32_t pos = slot_pos ? slot_pos[slot] : slot;   // (null: slot k reads image row k)
+    const int slot = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+    if (slot >= n_slots) return;
+    const int32_t pos = slot_pos[slot];
     if (pos < 0) {                              // padding slot
         if (lane == 0) {
-            if (S_out) S_out[slot] = 0.0;
-            if (mu_out) mu_out[slot] = 0.0;
-            if (rsd_out) rsd_out[slot] = 0.0;
+            mu_out[slot] = 0.0;
+            rsd_out[slot] = 0.0;
         }
         return;
     }
@@ -253,45 +314,30 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_snp_stats(
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t word = wv[u][j];
-                const uint32_t lo2 = word & 0x55555555u;
-                const uint32_t hi2 = (word >> 1) & 0x55555555u;
-                const int n_miss = __builtin_popcount(lo2 & ~hi2);
-                const int n_two = __builtin_popcount(~lo2 & ~hi2 & 0x55555555u);
-                const int n_one = __builtin_popcount(~lo2 & hi2);
-                nmiss += n_miss;
-                sum += 2 * n_two + n_one;
-                sq += 4 * n_two + n_one;
-            }
+            for (int j = 0; j < 4; ++j) count_word(wv[u][j], sum, sq, nmiss);
         }
     }
     sum = wave_sum_i32(sum);
     sq = wave_sum_i32(sq);
     nmiss = wave_sum_i32(nmiss);
     if (lane == 0) {
-        const double dc = static_cast<double>(n_ref - nmiss);       // observed calls
-        const double ds = static_cast<double>(sum);
-        const double mu = ds / dc;                                   // imputation value
-        const double css = static_cast<double>(sq) - ds * ds / dc;  // centred sum of squares
-        const double sd = sqrt(css / static_cast<double>(n_ref - 1));
-        if (S_out) S_out[slot] = ds;
-        if (mu_out) mu_out[slot] = mu;
-        if (rsd_out) rsd_out[slot] = 1.0 / sd;                      // +inf when monomorphic
-        if (nmiss > 0 && block_flags) atomicOr(block_flags + (slot_block ? slot_block[slot] : slot), 1);
+        double ds, mu, rsd;
+        row_moments(n_ref, sum, sq, nmiss, ds, mu, rsd);
+        mu_out[slot] = mu;
+        rsd_out[slot] = rsd;
     }
 }
 
 // ------------------------------------------------------------------------------------------
 // MAF of IO::readSNPIm as the reference rounds it (dtpr.cpp:356-362): missing calls take the
-// mean of the observed calls (mu, exact S / count from dbslmm_snp_stats), sum(geno) runs in
+// mean of the observed calls (mu, exact S / count from dbslmm_slot_stats), sum(geno) runs in
 // Armadillo's arrayops::accumulate order -- two sequential accumulators over the even / odd
 // individuals -- and af = 0.5 * sum / n.  Once a (non-integer) mean has been added, each later add
 // rounds, so the order decides the last bits, and the MAF filter of matchRef (|maf_ref - maf| <
 // mafMax, strict) can flip on them.  One thread per row: a sequential chain of n_ref fp64 adds,
 // rounded exactly like the host's (no reassociation).
 // ------------------------------------------------------------------------------------------
-// Rows without a missing call (miss[k] == 0; miss / S from dbslmm_snp_stats, optional) hold
+// Rows without a missing call (miss[k] == 0; miss / S from dbslmm_slot_stats, optional) hold
 // only integer dosages: every partial sum of that order is an exact integer, so a1 + a2 equals
 // the exact observed sum S and the chain is skipped (bit-identical).
 extern "C" __global__ __launch_bounds__(256) void dbslmm_maf_arma(

@@ -5,7 +5,9 @@
 //   image     the resident panel image (dbslmm_bed_repitch, made once per uploaded panel): the
 //             .bed rows without the magic bytes at a pitch of kpad / 4 bytes (64-B aligned rows),
 //             bits past individual n_ref - 1 set (PLINK 11 = dosage 0), one all-0xFF zero-dosage
-//             row at the end; raw PLINK codes in file order, shared by every plan on the panel
+//             row at the end; raw PLINK codes in file order, shared by every plan on the panel;
+//             behind it, in the same allocation, the row table: per row the exact integers
+//             {sum, sumsq, nmiss} the per-slot statistics are gathered from (dbslmm_slot_stats)
 //   slots     non-empty blocks, in block order, each padded to ld = roundup(m + 1, 32) slots:
 //             [small SNPs | large SNPs | padding]; per slot: bed row (-1 = pad), block,
 //             z-score, output index (>= 0 small, -1-i large); slot m of a block doubles as
@@ -46,10 +48,10 @@
 #include "pcg.hip"
 
 namespace {
-// events per timed run: [0] start, [1] after the statistics pass (slot name: unpack), [2] after gram, [3] after chol_large,
+// events per timed run: [0] start, [1] after the statistics gather (slot name: unpack), [2] after gram, [3] after chol_large,
 // [4] / [5] around chol_small (main stream), [6] / [8] around the tiled factorisation sequence,
 // [8] / [7] around the h2f Chebyshev iterations (stream2)
-constexpr int kEvPerRun = 12;   // 9, 10: around the lead group's Gram (between the halves of the statistics pass);
+constexpr int kEvPerRun = 12;   // 9, 10: around the lead group's Gram (between the statistics and [1]);
                                 // 11: the rest group's factorisation + backward done (its own
                                 // stream, split substitutions; else recorded with 8)
 constexpr size_t kCholLargeLds = sizeof(double) * chol::kLargeDoubles;
@@ -93,11 +95,17 @@ constexpr int kTrailSq = 8;             // 2D squares (in 128-tiles) per XCD of 
 
 int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 // The resident panel image (kernels.hip: dbslmm_bed_repitch): n_rows rows of `pitch` bytes and the
-// zero-dosage row n_rows, made for n_ref individuals.
+// zero-dosage row n_rows, made for n_ref individuals, followed IN THE SAME ALLOCATION by the row
+// table: one 16-byte entry {sum, sumsq, nmiss, 0} per row (the zero-dosage row's all zero), the
+// exact integers every per-row statistic derives from (dbslmm_slot_stats).  One allocation, so the
+// table lives exactly as long as the image bytes: shared by the context's cache and every plan
+// created from it, released with them.
 struct PanelImage {
     std::shared_ptr<uint8_t> mem;
     int64_t pitch = 0;
     int32_t n_rows = 0, n_ref = 0;
+    int64_t image_bytes() const { return (static_cast<int64_t>(n_rows) + 1) * pitch; }   // a multiple of 64
+    const v4i* rows() const { return reinterpret_cast<const v4i*>(mem.get() + image_bytes()); }
 };
 // Graph capture (launch_graph) vs the device-synchronising setup calls of another host thread
 // (multi-device plans run one thread per shard; several shards may share a device): a
@@ -188,8 +196,6 @@ struct dbslmm_plan {
     int32_t n_htiles = 0;
     int32_t n_htiles_lead = 0;         // ... of which the first n_htiles_lead are the lead group's,
     int32_t n_htiles_tiled = 0;        //     the first n_htiles_tiled the tiled blocks' (then the rest)
-    int32_t* d_slot_order = nullptr;   // lead group: [its slots | the others'] (their statistics run in that order)
-    int32_t n_slots_lead = 0;
     bool early_fork = false;           // every tiled block's Gram is in those: the tiled sequences
                                        // may start before the other blocks' Gram
     double* d_M = nullptr;
@@ -541,7 +547,7 @@ static hipError_t image_from_verbatim(dbslmm_ctx* ctx, const uint8_t* d_bed, int
     if (n_rows >= INT32_MAX) return hipErrorInvalidValue;
     const int64_t pitch = round_up(n_ref, gram::kKpadAlign) / 4;
     uint8_t* d = nullptr;
-    hipError_t e = hipMalloc(&d, static_cast<size_t>(n_rows + 1) * pitch);
+    hipError_t e = hipMalloc(&d, static_cast<size_t>(n_rows + 1) * (pitch + sizeof(v4i)));   // image | row table
     if (e != hipSuccess) return e;
     PanelImage im;
     im.mem = dev_shared(d, ctx->device);
@@ -549,7 +555,7 @@ static hipError_t image_from_verbatim(dbslmm_ctx* ctx, const uint8_t* d_bed, int
     im.n_rows = static_cast<int32_t>(n_rows);
     im.n_ref = n_ref;
     hipLaunchKernelGGL(dbslmm_bed_repitch, dim3(static_cast<unsigned>((n_rows + 1 + 3) / 4)), dim3(256), 0,
-                       ctx->stream, d_bed, n_ref, bps, im.n_rows, d, pitch);
+                       ctx->stream, d_bed, n_ref, bps, im.n_rows, d, pitch, const_cast<v4i*>(im.rows()));
     if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return e;
     *out = std::move(im);
     return hipSuccess;
@@ -962,7 +968,7 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
                     p->d_blk_id, p->d_row0, p->d_m, p->d_ms, p->d_ld, p->d_matoff, p->d_tiles,
                     p->d_M, p->d_beta_s, p->d_beta_l, p->d_tlist, p->d_btiles, p->d_htiles, p->d_dshift,
                     p->d_tlist_multi, p->d_tri_f, p->d_tri_b, p->d_foff, p->d_tflags, p->d_tb,
-                    p->d_cheb, p->d_coef, p->d_stamps, p->d_slot_order, p->d_tepi, p->d_cheb_items,
+                    p->d_cheb, p->d_coef, p->d_stamps, p->d_tepi, p->d_cheb_items,
                     p->d_tcheb_blocks, p->d_cgrec, p->d_cgconv, p->d_cgit, p->d_G16, p->d_pblk,
                     p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
                     p->d_pitb, p->d_pdone, p->d_pact, p->d_off16, p->d_ld16, p->d_pflist, p->d_pfnext};
@@ -1257,20 +1263,6 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
             build_tiled(mv, tb_rest, 1, p->n_nonempty, p->tl_rest, tlist);
         }
     }
-    // lead group: the statistics of its slots run first, so its Gram (and sequence) need not wait for the
-    // whole pass
-    std::vector<int32_t> slot_order;
-    if (!p->tl_rest.empty()) {
-        std::vector<char> in_lead(p->n_nonempty, 0);
-        for (int32_t b = 0; b < p->n_nonempty; ++b) in_lead[b] = mv[b] >= lead_min;
-        for (int32_t b = 0; b < p->n_nonempty; ++b)
-            if (in_lead[b])
-                for (int32_t r = row0[b]; r < row0[b] + ldv[b]; ++r) slot_order.push_back(r);
-        p->n_slots_lead = static_cast<int32_t>(slot_order.size());
-        for (int32_t b = 0; b < p->n_nonempty; ++b)
-            if (!in_lead[b])
-                for (int32_t r = row0[b]; r < row0[b] + ldv[b]; ++r) slot_order.push_back(r);
-    }
     // substitution work lists (trsv.hip): 64-row tiles of the tiled blocks; forward in order of
     // (tile, block), backward in order of (tiles from the end, block) -- every dependency of an
     // item comes earlier in its list
@@ -1362,8 +1354,9 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     }
     const double n_snp = static_cast<double>(p->n_s + p->n_l);
     p->wl[0] = n_snp;
-    p->wl[1] = n_snp * bps;
-    // bytes the statistics pass writes: S, mu, 1/sd per slot and the blocks' missing-call flags
+    // bytes the statistics gather reads per slot: its image row, the row's table entry, its block
+    p->wl[1] = static_cast<double>(p->n_slots) * (sizeof(int32_t) + sizeof(v4i) + sizeof(int32_t));
+    // bytes it writes: S, mu, 1/sd per slot and the blocks' missing-call flags
     p->wl[2] = static_cast<double>(p->n_slots) * 3 * sizeof(double) + static_cast<double>(p->n_nonempty) * sizeof(int32_t);
     p->wl[3] = ops_alg;
     p->wl[4] = ops_exec;
@@ -1414,7 +1407,6 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     if ((e = dev_upload(&p->d_tri_b, tri_b, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
     if ((e = dev_upload(&p->d_foff, foff, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
     if ((e = dev_upload(&p->d_tb, p->h_tb, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if (!slot_order.empty() && (e = dev_upload(&p->d_slot_order, slot_order, ctx->stream)) != hipSuccess) return fail("upload slot order");
     if (!tcheb_list.empty() && (e = dev_upload(&p->d_tcheb_blocks, tcheb_list, ctx->stream)) != hipSuccess)
         return fail("upload trsv lists");
     // [tile flags | ticket counter | error word | spare]
@@ -1472,7 +1464,7 @@ static int collect_timing(dbslmm_plan* p) {
             span[DBSLMM_K_PCG_BLOCK] = t[4] - t[3];   // (inside the PCG span, on the second stream)
         }
         for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
-        // the lead group's Gram (9 -> 10) sits between the two statistics launches (0 -> 1)
+        // the lead group's Gram (9 -> 10) sits inside the statistics span (0 -> 1)
         float lg = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&lg, e[9], e[10]));
         p->ms_acc[0] -= lg;
@@ -2352,9 +2344,9 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
         hipLaunchKernelGGL(dbslmm_set_scalar, dim3(1), dim3(1), 0, s, p->d_dshift + c,
                            1.0 / (sigmas[c] * static_cast<double>(p->n_obs)));
     if (p->n_slots > 0)
-        hipLaunchKernelGGL(dbslmm_snp_stats, dim3((p->n_slots + 3) / 4), dim3(256), 0, s, p->d_img, p->n_ref,
-                           p->img.pitch, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
-                           p->d_flags, nullptr);
+        hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, s, p->img.rows(),
+                           p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
+                           p->d_flags);
     HIP_TRY(ctx, hipGetLastError());
     if (ev) for (int k : {1, 9, 10}) HIP_TRY(ctx, hipEventRecord(ev[k], s));
     uint16_t* g16 = p->pcg_g16 ? p->d_G16 : nullptr;
@@ -2530,18 +2522,12 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     if (front) HIP_TRY(ctx, hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), s));
     HIP_TRY(ctx, hipMemsetAsync(p->d_status, 0, n * nbk * sizeof(int32_t), s));
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[0], s));
-    auto stats = [&](const int32_t* list, int32_t n_sl) {
-        const int wpb = 4;
-        dim3 grid((n_sl + wpb - 1) / wpb);
-        hipLaunchKernelGGL(dbslmm_snp_stats, grid, dim3(256), 0, s, p->d_img, p->n_ref,
-                           p->img.pitch, p->d_slot_pos, p->d_slot_block, n_sl, p->d_S, p->d_mu,
-                           p->d_rsd, p->d_flags, list);
-    };
-    // a lead group's slots first: its Gram and sequence start after ~2 % of the pass
-    const bool split_stats = front && p->n_slots_lead > 0;
+    // the statistics of every slot in one launch (a gather from the image's row table: microseconds,
+    // so a lead group's Gram right behind it starts at once)
     if (front && p->n_slots > 0) {
-        if (split_stats) stats(p->d_slot_order, p->n_slots_lead);
-        else stats(nullptr, p->n_slots);
+        hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, s, p->img.rows(),
+                           p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
+                           p->d_flags);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[9], s));
@@ -2583,11 +2569,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
         debug_spin(p, s, 1);
     }
-    if (split_stats) {   // the other slots
-        stats(p->d_slot_order + p->n_slots_lead, p->n_slots - p->n_slots_lead);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));   // (statistics = 0 -> 1 less the lead Gram 9 -> 10)
     // the other tiled blocks' Gram tiles next: with early_fork their sequence (and the single
     // sequence without a lead group) forks here, before the non-tiled blocks' Gram
     if (front && p->n_htiles_tiled > p->n_htiles_lead) {
@@ -3124,8 +3106,7 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
             hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cpitch + 255) / 256), p->n_slots),
                                dim3(256), 0, st, d_tbed, tbps, d_tpos, p->n_slots, d_sel, n_test, cpitch, d_cbed);
             hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
-                               st, d_cbed, n_test, cpitch, d_cpos, d_cpos, p->n_slots, nullptr, d_mu, d_rsd,
-                               nullptr, nullptr);
+                               st, d_cbed, n_test, cpitch, d_cpos, p->n_slots, d_mu, d_rsd);
             hipLaunchKernelGGL(dbslmm_variance, dim3(static_cast<unsigned>(nt_pad / 64), p->n_nonempty),
                                dim3(256), 0, st, p->d_M + p->var_copy * p->M_elems, p->d_row0, p->d_m,
                                p->d_ms, p->d_ld, p->d_matoff, p->d_blk_id, p->d_status + p->var_copy * p->nbk,
@@ -3173,10 +3154,11 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
         double* d_maf = d_S + n_snp;
         int32_t* d_miss = reinterpret_cast<int32_t*>(d_maf + n_snp);
         const uint8_t* db = im.mem.get();
-        // row k = image row k (null row lists); per-row missing-call flags (row k's "block" is k)
-        hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((n_snp + 3) / 4)), dim3(256), 0,
-                           ctx->stream, db, n_ref, im.pitch, nullptr, nullptr, static_cast<int32_t>(n_snp),
-                           d_S, d_mu, nullptr, d_miss, nullptr);
+        // from the image's row table: row k = image row k (null row lists); per-row missing-call
+        // flags (row k's "block" is k)
+        hipLaunchKernelGGL(dbslmm_slot_stats, dim3(static_cast<unsigned>((n_snp + 255) / 256)), dim3(256), 0,
+                           ctx->stream, im.rows(), n_ref, nullptr, nullptr, static_cast<int32_t>(n_snp),
+                           d_S, d_mu, nullptr, d_miss);
         hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_snp + 255) / 256)), dim3(256), 0,
                            ctx->stream, db, n_ref, im.pitch, nullptr, static_cast<int32_t>(n_snp), d_mu, d_maf,
                            d_S, d_miss);
@@ -3189,6 +3171,31 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
     } while (0);
     (void)hipFree(d_work);
     return rc;
+}
+
+// The row table of the panel's image, rows [0, n_rows): the exact integers {sum, sumsq, nmiss}.
+int dbslmm_bed_row_stats(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
+                         int64_t n_rows, int32_t* out) {
+    if (!ctx) return DBSLMM_E_ARG;
+    ON_FIRST_DEVICE(ctx, dbslmm_bed_row_stats(ctx0_, bed, bed_len, n_ref, n_rows, out));
+    ARG_CHECK(ctx, bed && out && n_ref > 1 && n_rows >= 0 && n_rows < INT32_MAX, "bad arguments");
+    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
+    ARG_CHECK(ctx, bed_len >= 3 + n_rows * bps, "bed image shorter than n_rows rows");
+    if (n_rows == 0) return DBSLMM_OK;
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PanelImage im;
+    hipError_t e = panel_image(ctx, bed, bed_len, n_ref, &im);
+    std::vector<int32_t> h(static_cast<size_t>(n_rows) * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), im.rows(), h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        ctx->err = std::string("bed_row_stats: ") + hipGetErrorString(e);
+        return DBSLMM_E_HIP;
+    }
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int k = 0; k < 3; ++k) out[3 * r + k] = h[4 * r + k];
+    return DBSLMM_OK;
 }
 
 int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
@@ -3222,8 +3229,8 @@ int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             break;
         }
         const uint8_t* db = im.mem.get();
-        hipLaunchKernelGGL(dbslmm_snp_stats, dim3((n_rows + 3) / 4), dim3(256), 0, ctx->stream,
-                           db, n_ref, im.pitch, d_pos, d_pos, n_rows, nullptr, d_mu, d_rsd, nullptr, nullptr);
+        hipLaunchKernelGGL(dbslmm_slot_stats, dim3((n_rows + 255) / 256), dim3(256), 0, ctx->stream,
+                           im.rows(), n_ref, d_pos, nullptr, n_rows, nullptr, d_mu, d_rsd, nullptr);
         hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
                            ctx->stream, db, n_ref, im.pitch, d_pos, n_rows, d_mu, d_maf, nullptr, nullptr);
         hipLaunchKernelGGL(dbslmm_std_columns, dim3(static_cast<unsigned>((n_out + 255) / 256)),
@@ -3294,9 +3301,9 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
         }
         const uint8_t* db = im.mem.get();
         if (n_rows > 0)
-            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((n_rows + 3) / 4)), dim3(256), 0,
-                               ctx->stream, db, n_ref, im.pitch, d_pos, d_pos, static_cast<int32_t>(n_rows),
-                               nullptr, d_mu, d_rsd, nullptr, nullptr);
+            hipLaunchKernelGGL(dbslmm_slot_stats, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
+                               ctx->stream, im.rows(), n_ref, d_pos, nullptr, static_cast<int32_t>(n_rows),
+                               nullptr, d_mu, d_rsd, nullptr);
         hipLaunchKernelGGL(dbslmm_valid_partial, dim3(n_chunks, num_block), dim3(256), 0, ctx->stream,
                            db, n_ref, im.pitch, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks);
         hipLaunchKernelGGL(dbslmm_valid_reduce, dim3((num_block + 255) / 256), dim3(256), 0, ctx->stream,

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 15
+#define DBSLMM_ABI_VERSION 16
 
 enum {
     DBSLMM_OK = 0,
@@ -199,7 +199,8 @@ typedef struct dbslmm_problem {
 
 /* Kernel timing slots reported by dbslmm_plan_kernel_ms. */
 enum {
-    DBSLMM_K_UNPACK = 0,      /* dbslmm_snp_stats: per-SNP statistics of the slots' 2-bit panel rows
+    DBSLMM_K_UNPACK = 0,      /* dbslmm_slot_stats: per-SNP statistics of the slots, gathered from
+                                 the panel image's row table
                                  (the slot keeps the name of the unpack that used to run here) */
     DBSLMM_K_GRAM = 1,        /* dbslmm_gram_i8 / _big / _huge: FP4-MFMA grouped syrk of the exact
                                  integer dosages (raw 2-bit panel rows gathered, decoded and
@@ -333,8 +334,9 @@ void dbslmm_plan_destroy(dbslmm_plan* plan);
 int dbslmm_plan_enable_timing(dbslmm_plan* plan, int enable);
 int dbslmm_plan_kernel_ms(dbslmm_plan* plan, double* ms_out /*[DBSLMM_K_COUNT]*/, int32_t* launches_out);
 
-/* Workload figures of the plan (for rooflines): [0] SNPs, [1] packed bytes read by the statistics
- * pass, [2] bytes it writes (S, mean, 1/sd per slot and the blocks' missing-call flags), [3] Gram ops (2 per MAC, algorithmic
+/* Workload figures of the plan (for rooflines): [0] SNPs, [1] bytes read by the statistics
+ * gather (per slot: its row position, the row's 16-byte table entry, its block id), [2] bytes it
+ * writes (S, mean, 1/sd per slot and the blocks' missing-call flags), [3] Gram ops (2 per MAC, algorithmic
  * sum_b n_ref*m_b*(m_b+1)), [4] Gram ops as executed on padded tiles, [5] Cholesky+solve fp64
  * flops of the large blocks (sum_b m_b^3/3 + 2 m_b^2), [6] non-empty blocks, [7] gram tiles,
  * [8] the same fp64 flops for the small blocks, [9] large blocks, [10] the same fp64 flops for
@@ -392,6 +394,15 @@ int dbslmm_plan_variance(dbslmm_plan* plan, const dbslmm_test_panel* test, doubl
 /* MAF pass: maf[r] for every bed row r < n_snp (readSNPIm with an all-ones indicator). */
 int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
                    int64_t n_snp, double* maf);
+
+/* The row table of the panel image (ABI 16; tests and diagnostics): out[3 r .. 3 r + 2] = the exact
+ * integers {dosage sum, sum of squared dosages, missing calls} of bed row r < n_rows over the
+ * n_ref individuals -- what the image keeps per row and every per-row statistic (the plans' S, mean
+ * and 1/sd, bed_maf, read_snp_std, valid_blocks) derives from.  Pad bits of a row's last byte never
+ * count.  Same panel-key rules as dbslmm_bed_maf (the context's cached image when (bed, bed_len)
+ * is its key, else an upload of its own); a multi-device context answers from its first device. */
+int dbslmm_bed_row_stats(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
+                         int64_t n_rows, int32_t* out /* n_rows x 3: sum, sumsq, nmiss */);
 
 /* readSNPIm + nomalizeVec for rows pos[0..n_rows): out is n_ref x n_rows column-major fp64
  * (column j = standardised dosages of bed row pos[j]); maf (optional) n_rows entries. */

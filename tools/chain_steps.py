@@ -7,7 +7,7 @@ import sys
 
 t = list(csv.DictReader(open(sys.argv[1])))
 t.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))]
+idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))]
 last = t[idx[-2]:]
 t0 = int(last[0]["Start_Timestamp"])
 by = collections.defaultdict(list)

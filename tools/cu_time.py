@@ -4,10 +4,10 @@ d=collections.OrderedDict()
 for r in rows:
     e=d.setdefault(int(r['Dispatch_Id']),dict(r)); e[r['Counter_Name']]=float(r['Counter_Value'])
 ds=sorted(d.values(), key=lambda e:int(e['Dispatch_Id']))
-idx=[i for i,e in enumerate(ds) if e['Kernel_Name'].startswith(('dbslmm_snp_stats', 'dbslmm_unpack'))]
+idx=[i for i,e in enumerate(ds) if e['Kernel_Name'].startswith(('dbslmm_slot_stats', 'dbslmm_snp_stats', 'dbslmm_unpack'))]
 last=ds[idx[-2]:]
 cap={'dbslmm_tchol_trailing3k16':16,'dbslmm_tchol_region':4,'dbslmm_tchol_panel':8,'dbslmm_gram_huge':8,'dbslmm_gram_big':8,
-'dbslmm_gram_i8':32,'dbslmm_chol_large':4,'dbslmm_chol_cheb':8,'dbslmm_trsv_bwd':9,'dbslmm_trsv_fwd':9,'dbslmm_snp_stats':32,'dbslmm_unpack_stats':32,'dbslmm_chol_small':8,'dbslmm_cheb_init':32}
+'dbslmm_gram_i8':32,'dbslmm_chol_large':4,'dbslmm_chol_cheb':8,'dbslmm_trsv_bwd':9,'dbslmm_trsv_fwd':9,'dbslmm_snp_stats':32,'dbslmm_slot_stats':32,'dbslmm_unpack_stats':32,'dbslmm_chol_small':8,'dbslmm_cheb_init':32}
 agg=collections.defaultdict(lambda:[0,0.,0.])
 clk=2.4e9
 for e in last:

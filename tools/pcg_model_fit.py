@@ -56,7 +56,9 @@ def main(cal, prof=None):
         gb = per_run.get("dbslmm_gram_big", 0) + per_run.get("dbslmm_gram_i8", 0)
         print(f"  gram huge {gh:8.1f} us -> {ops[m >= hm].sum() / gh * 1e-9 * 1e3 / 1e3:.3f} Pops/s;"
               f" big {gb:8.1f} us -> {ops[m < hm].sum() / max(gb, 1e-9) * 1e-9:.3f} Pops/s")
-        if "dbslmm_snp_stats" in per_run:               # the statistics pass reads the image rows
+        if "dbslmm_slot_stats" in per_run:              # a gather from the image's row table: 48 B per slot
+            up, ub = per_run["dbslmm_slot_stats"], m.sum() * 48
+        elif "dbslmm_snp_stats" in per_run:             # round 7: the statistics pass read the image rows
             up, ub = per_run["dbslmm_snp_stats"], m.sum() * math.ceil(n_ref / 256) * 64
         else:                                           # traces up to round 6: the unpack also wrote Gp
             up, ub = per_run.get("dbslmm_unpack_stats", 0), m.sum() * (math.ceil(n_ref / 4) + kp / 4)

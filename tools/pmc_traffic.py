@@ -8,7 +8,7 @@ Also records launches per kernel and, for the composite phases the bench times a
 the tiled Cholesky (dbslmm_tchol_* launches plus the persistent backward substitution
 dbslmm_trsv_bwd<1>) and the h2f substitutions (dbslmm_trsv_fwd/bwd<2>) -- the summed
 HBM bytes per run (= per bench step; runs = launches of dbslmm_pcg_init on the PCG route, else of
-dbslmm_gram_i8, one per run -- the unpack is two launches per run with a lead group) under
+dbslmm_gram_i8, one per run) under
 "dbslmm_tchol" and "dbslmm_trsv", and likewise the Gram launches under "dbslmm_gram" and the
 chip-wide PCG launches under "dbslmm_pcg" (key "hbm_bytes_per_step").
 """
@@ -32,7 +32,7 @@ def main(src, dst, bench_args=""):
     f = per_kernel(os.path.join(src, "fetch_counter_collection.csv"))
     w = per_kernel(os.path.join(src, "write_counter_collection.csv"))
     out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over "
-                     f"`python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline {bench_args}`".rstrip(),
+                     f"`python3 bench.py --steps 5 --warmup 2 {bench_args}`".rstrip(),
            "correction": "hbm_bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 per launch",
            "kernels": {}}
     # runs: one dbslmm_pcg_init per run on the PCG route, else one dbslmm_gram_i8
@@ -48,7 +48,7 @@ def main(src, dst, bench_args=""):
             seq += (2 * fk + wk) * 1024.0 * n
         elif name.startswith("dbslmm_trsv_"):
             trsv += (2 * fk + wk) * 1024.0 * n
-        if name == "dbslmm_snp_stats":
+        if name in ("dbslmm_slot_stats", "dbslmm_snp_stats"):   # (round 7: snp_stats read the image rows)
             stats += (2 * fk + wk) * 1024.0 * n
         if name.startswith("dbslmm_gram_"):
             gram += (2 * fk + wk) * 1024.0 * n
@@ -62,7 +62,7 @@ def main(src, dst, bench_args=""):
                                              note="h2f substitutions (CG by default), per run")
     if runs and stats:   # the bench's timing slot of the statistics pass keeps the unpack's name
         out["kernels"]["dbslmm_unpack_stats"] = dict(hbm_bytes_per_step=stats / runs, runs=runs,
-                                                     note="dbslmm_snp_stats launches, per run")
+                                                     note="dbslmm_slot_stats launches, per run")
     if runs and gram:
         out["kernels"]["dbslmm_gram"] = dict(hbm_bytes_per_step=gram / runs, runs=runs,
                                              note="dbslmm_gram_huge / _big / _i8 launches, per run")

@@ -1,7 +1,7 @@
 import csv,collections,sys
 t=list(csv.DictReader(open(sys.argv[1])))
 t.sort(key=lambda r:int(r["Start_Timestamp"]))
-idx=[i for i,r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))]
+idx=[i for i,r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))]
 last=t[idx[-2]:]
 t0=int(last[0]["Start_Timestamp"])
 by=collections.defaultdict(lambda: collections.defaultdict(lambda:[1e18,0,0,0.0]))

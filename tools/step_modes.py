@@ -7,7 +7,7 @@ import sys
 
 t = list(csv.DictReader(open(sys.argv[1])))
 t.sort(key=lambda r: int(r["Start_Timestamp"]))
-starts = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))][::2]
+starts = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))][::2]
 for n, i0 in enumerate(starts):
     i1 = starts[n + 1] if n + 1 < len(starts) else len(t)
     seg = t[i0:i1]
@@ -17,7 +17,7 @@ for n, i0 in enumerate(starts):
              if r["Kernel_Name"].replace("void ", "").startswith(pfx) and (q is None or r["Queue_Id"] == q)]
         return (min(a for a, _ in v) / 1e6, max(b for _, b in v) / 1e6) if v else (0, 0)
     un = [(int(r["Start_Timestamp"]) - t0, int(r["End_Timestamp"]) - t0, r["Queue_Id"]) for r in seg
-          if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))]
+          if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))]
     gh = [(int(r["Start_Timestamp"]) - t0, int(r["End_Timestamp"]) - t0, r["Queue_Id"]) for r in seg
           if r["Kernel_Name"].startswith("dbslmm_gram_huge")]
     end = max(int(r["End_Timestamp"]) for r in seg) - t0

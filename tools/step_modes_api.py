@@ -7,7 +7,7 @@ for i in (1,2,3,4):
     k=list(csv.DictReader(open(base+'/run_kernel_trace.csv'))); k.sort(key=lambda r:int(r['Start_Timestamp']))
     a=list(csv.DictReader(open(base+'/run_hip_api_trace.csv'))); a.sort(key=lambda r:int(r['Start_Timestamp']))
     nm=lambda r:r['Kernel_Name'].replace('void ','').split('(')[0]
-    idx=[j for j,r in enumerate(k) if nm(r).startswith(('dbslmm_snp_stats', 'dbslmm_unpack'))]
+    idx=[j for j,r in enumerate(k) if nm(r).startswith(('dbslmm_slot_stats', 'dbslmm_snp_stats', 'dbslmm_unpack'))]
     gl=[r for r in a if r['Function']=='hipGraphLaunch']
     print(f'p{i}: graph launches {len(gl)}')
     for s in range(0,len(idx)-1,2):

@@ -10,7 +10,7 @@ t = list(csv.DictReader(open(sys.argv[1])))
 t.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last step starts at its unpack; a plan with a lead group unpacks in two launches per step
 # (its slots first)
-idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))]
+idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))]
 st = lambda i: int(t[i]["Start_Timestamp"])
 first = idx[-2] if len(idx) > 1 and st(idx[-1]) - st(idx[-2]) < 5_000_000 else idx[-1]
 name = lambda r: r["Kernel_Name"].replace("void ", "").split("(")[0]

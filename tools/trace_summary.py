@@ -6,7 +6,7 @@ import sys
 path = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/prof_c3/run_kernel_trace.csv"
 show = int(sys.argv[2]) if len(sys.argv) > 2 else 12
 t = list(csv.DictReader(open(path)))
-idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_snp_stats", "dbslmm_unpack"))]
+idx = [i for i, r in enumerate(t) if r["Kernel_Name"].startswith(("dbslmm_slot_stats", "dbslmm_snp_stats", "dbslmm_unpack"))]
 last = t[idx[-1]:]
 t0 = int(last[0]["Start_Timestamp"])
 agg = collections.defaultdict(lambda: [0, 0])
