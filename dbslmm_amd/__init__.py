@@ -109,7 +109,9 @@ class BlockProblem:
     tau: float = 0.8
     # dbslmm_options (path-selection thresholds; missing keys = the library defaults):
     # tiled_min, gram_big_min, gram_huge_min, h2f_mode (0 auto / 1 merged), cheb_tol, lead_min,
-    # ..., solver (0 auto / 1 factorisation / 2 PCG), pcg_tol, pcg_maxit
+    # ..., solver (0 auto / 1 factorisation / 2 PCG), pcg_tol, pcg_maxit, stream_out (PCG route of
+    # run_multi: 1 = results copied out block by block while the GPU iterates, the default; 0 = the
+    # download after the run)
     opts: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -141,7 +143,10 @@ class BlockProblem:
         unknown = set(self.opts) - {f[0] for f in _lib.Options._fields_}
         if unknown:
             raise ValueError(f"unknown dbslmm_options fields: {sorted(unknown)}")
-        self._opts = _lib.Options(**self.opts)     # kept alive with the problem
+        o = dict(self.opts)
+        if "stream_out" in o and int(o["stream_out"]) == 0:
+            o["stream_out"] = -1                   # here 1 / 0 read on / off (the struct's 0 is "default": on)
+        self._opts = _lib.Options(**o)             # kept alive with the problem
         return _lib.Problem(
             _ptr(self.bed), self.bed.size, self.n_ref, self.n_obs, self.sigma_s, self.tau,
             self.num_block, _ptr(self.s_ptr), _ptr(self.s_pos), _ptr(self.z_s),
@@ -306,6 +311,21 @@ class DBSLMMFIT:
         self.ctx.check(self.ctx.lib.dbslmm_est(self.ctx.h, C.byref(cs), _ptr(bs), _ptr(bl), _ptr(st)),
                        "dbslmm_est")
         return bs, bl, st
+
+
+def out_ranges(s_ptr, l_ptr=None) -> np.ndarray:
+    """The table a streamed run copies finished blocks out by (dbslmm_out_ranges; host only, no
+    GPU): one row {block, s0, s1, l0, l1} per non-empty block, in block order."""
+    lib = _lib.load()
+    sp = np.ascontiguousarray(s_ptr, dtype=np.int64)
+    lp = None if l_ptr is None else np.ascontiguousarray(l_ptr, dtype=np.int64)
+    nb = len(sp) - 1
+    out = np.zeros((max(1, nb), 5), dtype=np.int64)
+    n = np.zeros(1, dtype=np.int32)
+    rc = lib.dbslmm_out_ranges(nb, _ptr(sp), _ptr(lp), _ptr(out), _ptr(n))
+    if rc != 0:
+        raise DbslmmError(f"dbslmm_out_ranges failed rc={rc}")
+    return out[:int(n[0])]
 
 
 def bed_maf(ctx: Context, bed: np.ndarray, n_ref: int, n_snp: int) -> np.ndarray:

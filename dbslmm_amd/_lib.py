@@ -21,10 +21,10 @@ EXPORTS = (
     "dbslmm_ctx_create_multi", "dbslmm_ctx_num_devices", "dbslmm_plan_shard_info",
     "dbslmm_ctx_cache_bed", "dbslmm_ctx_cache_bed_fd", "dbslmm_plan_block_matrix",
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
-    "dbslmm_plan_block_iters", "dbslmm_bed_row_stats",
+    "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges",
 )
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
@@ -42,7 +42,7 @@ class Options(C.Structure):
         ("debug_stop", C.c_int32), ("sub_split", C.c_int32), ("sub_grid_lead", C.c_int32),
         ("sub_grid_rest", C.c_int32), ("shard_copies", C.c_int32), ("h2f_iter", C.c_int32),
         ("solver", C.c_int32), ("pcg_tol", C.c_double), ("pcg_maxit", C.c_int32),
-        ("pcg_whole", C.c_int32),
+        ("pcg_whole", C.c_int32), ("stream_out", C.c_int32),
     ]
 
 
@@ -113,6 +113,7 @@ def load(path: str | None = None):
     L.dbslmm_plan_create_units.argtypes = [V, P(Problem), C.c_int32, V, C.c_int32, P(V)]
     L.dbslmm_shard_plan_problem.argtypes = [P(Problem), V, C.c_int32, C.c_int32, V, V]
     L.dbslmm_plan_block_iters.argtypes = [V, V]
+    L.dbslmm_out_ranges.argtypes = [C.c_int32, V, V, V, V]
     if hasattr(L, "dbslmm_plan_block_matrix"):   # (tools/race_probe.py loads older builds for A/B)
         L.dbslmm_plan_block_matrix.argtypes = [V, C.c_int32, C.c_int32, V, V]
     if L.dbslmm_abi_version() != ABI_VERSION:

@@ -43,7 +43,10 @@
 //                      workgroup of the block), the stopping test, alpha / beta (Chronopoulos-Gear
 //                      form: one reduction phase per iteration), p, s, x, r.
 //   dbslmm_pcg_init / dbslmm_pcg_final   right-hand sides and state; beta = x / sqrt(n) in the
-//                      caller's order, status per copy.
+//                      caller's order, status per copy, for the blocks still without results at
+//                      the end of a chunk: monomorphic ones and those at the iteration cap (a
+//                      block dbslmm_pcg_block solves whole writes its own at the end of its
+//                      sequence, one that converges on the chip-wide kernels in dbslmm_pcg_update).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -103,9 +106,19 @@ struct PcgArgs {
     int32_t* itb;                   // per block: rows launches since init
     int32_t* done;                  // per block: 0 iterating, 1 converged, 2 monomorphic
     int32_t* active;                // blocks still iterating
+    int32_t* fin;                   // per block: tile rows that have written a converged block's results
     double* beta_s;
     double* beta_l;
     int32_t* status;
+    // a streamed run (dbslmm_options.stream_out): the host-visible mirror of beta_s / beta_l /
+    // status (the same copy-major layout and strides, coherent pinned memory) that every result
+    // is written to as well, and one flag per (route block, copy), [block * ncopy + copy], set to
+    // run_no once dbslmm_pcg_block has finished that pair; null otherwise
+    double* mir_s;
+    double* mir_l;
+    int32_t* mir_st;
+    int32_t* mir_flag;
+    int32_t run_no;                 // the plan's streamed-run number (never 0: a stale flag never matches)
     int64_t vstride;                // elements per copy-major vector array
     int64_t ns, nl, nbk;            // beta / status strides per copy
     double tau, rn, c0, tol, inv_sqrt_n;
@@ -225,6 +238,29 @@ __device__ __forceinline__ double jdiag(const PcgArgs& a, const PcgBlk& B, int i
 // the shift of product column k (the seed's on a multi-shift block)
 __device__ __forceinline__ double col_shift(const PcgArgs& a, const PcgBlk& B, int k) {
     return a.dshift[B.mshift ? a.seed : k];
+}
+
+// A finished solve's results, written by whichever kernel ends the block's iterations
+// (dbslmm_pcg_block at the end of a sequence, dbslmm_pcg_final for every other block): copy k's
+// beta = x / sqrt(n) of block slot i in the caller's order (NaN for a monomorphic block), and copy
+// k's block status from cnv -- each to the device arrays and, on a streamed run, to the mirror.
+__device__ __forceinline__ void put_beta(const PcgArgs& a, const PcgBlk& B, int i, int k, double x, bool mono) {
+    const int so = a.slot_out[B.row0 + i];
+    const double bv = mono ? __builtin_nan("") : x * a.inv_sqrt_n;
+    if (so >= 0) {
+        a.beta_s[k * a.ns + so] = bv;
+        if (a.mir_s) a.mir_s[k * a.ns + so] = bv;
+    } else {
+        a.beta_l[k * a.nl - 1 - so] = bv;
+        if (a.mir_l) a.mir_l[k * a.nl - 1 - so] = bv;
+    }
+}
+__device__ __forceinline__ void put_status(const PcgArgs& a, const PcgBlk& B, int k, bool mono) {
+    const int st = mono ? DBSLMM_BLOCK_MONOMORPHIC
+                        : a.cnv[B.sco + k] == 0 ? DBSLMM_BLOCK_NOT_CONVERGED : DBSLMM_BLOCK_OK;
+    const int64_t o = k * a.nbk + a.blk_id[B.blk];
+    a.status[o] = st;
+    if (a.mir_st) a.mir_st[o] = st;
 }
 
 // uint16 -> fp64 of the low / high half of a dword.  Volatile asm: the conversions stay inside the
@@ -478,6 +514,7 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_init(PcgA
         }
         if (tid == 0) {
             a.itb[bi] = 0;
+            a.fin[bi] = 0;
             const bool fz = B.fused && u16;       // solved whole by dbslmm_pcg_block
             a.done[bi] = mono_s ? 2 : fz ? 3 : 0;
             if (!mono_s && !fz) atomicAdd(a.active, 1);
@@ -626,8 +663,9 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_rows(PcgA
 // ------------------------------------------------------------------------------------------
 // The iteration's coefficients and update for one tile row.  Every workgroup of a block sums the
 // block's dots in the same order, so every tile row takes the same decisions; tile row 0 alone
-// writes the recurrence state (the other parity than the one read), the convergence iteration
-// and the block's done flag.
+// writes the recurrence state (the other parity than the one read) and the convergence iteration;
+// once every copy has converged the tile rows write the block's results and the last of them to
+// do so sets the block's done flag.
 //   per-copy blocks: Jacobi-PCG per copy in the Chronopoulos-Gear form
 //       gamma = r.u, delta = w.u, beta = gamma / gamma_prev, alpha = gamma / (delta - beta gamma / alpha_prev)
 //       p = u + beta p, s = w + beta s, x += alpha p, r -= alpha s
@@ -736,9 +774,26 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_update(Pc
     int running = 0;
     for (int k = 0; k < n; ++k) running += run_s[k];
     if (running == 0) {
-        if (I == 0 && tid == 0) {
+        // The block has converged, and every tile row of it takes this branch in this launch: each
+        // writes its rows' betas (x is final: a converged copy is no longer updated), tile row 0
+        // the status (put_beta / put_status, as dbslmm_pcg_final would at the end of the chunk),
+        // so a streamed run's host can copy the block out while the others still iterate.  The
+        // tile rows count in (release / acquire at device scope); the last one marks the block
+        // done -- after every tile row has passed its done test above -- and releases its flags
+        // at system scope.
+        const int r = tid & (kT - 1), h = tid >> 7, i = I * kT + r;
+        if (i < B.m)
+            for (int k = h; k < n; k += 2) put_beta(a, B, i, k, a.X[k * a.vstride + B.vo + i], false);
+        if (I == 0 && tid < n) put_status(a, B, tid, false);
+        __syncthreads();
+        if (tid == 0 &&
+            __hip_atomic_fetch_add(a.fin + bi, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == B.Tb - 1) {
             a.done[bi] = 1;
             atomicSub(a.active, 1);
+            if (a.mir_flag)
+                for (int c = 0; c < n; ++c)
+                    __hip_atomic_store(a.mir_flag + static_cast<int64_t>(bi) * n + c, a.run_no, __ATOMIC_RELEASE,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
         }
         return;
     }
@@ -811,9 +866,10 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_update(Pc
 // atomics), then w, the dots, the coefficients, the convergence test and the update exactly as
 // dbslmm_pcg_rows / dbslmm_pcg_update compute them -- with no partial slots, no per-iteration
 // launches and no hand-off between workgroups.  Thread t owns slots t + 256 q (q < kFPer): r, s
-// and w in registers, U = rsd o u and x and p of every copy in LDS (x goes to the block's global
-// vectors at the end).  The chip-wide kernels skip these blocks (init marks them
-// done = 3); dbslmm_pcg_final writes their betas and status from x and cnv as for the others.
+// and w in registers, U = rsd o u and x and p of every copy in LDS.  The chip-wide kernels skip these
+// blocks (init marks them done = 3), dbslmm_pcg_final too: the sequence writes its own betas and
+// status at its end (put_beta / put_status, as dbslmm_pcg_final does for the others), so a
+// streamed run's results leave the GPU block by block while the kernel runs.
 // ------------------------------------------------------------------------------------------
 #ifndef PCG_BLOCK_DEPTH
 #define PCG_BLOCK_DEPTH 3   // quadrant buffers per wave in dbslmm_pcg_block (2: one in flight)
@@ -849,7 +905,7 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
     double* yw = blds;                       // [4][kFRows] per-wave product sums
     double* Ul = blds + 4 * kFRows;          // [kFRows] rsd o u
     const int n = a.ncopy;
-    double* Xl = Ul + kFRows;                // [copy][kFRows] x (to global at the end)
+    double* Xl = Ul + kFRows;                // [copy][kFRows] x (the betas at the end)
     double* Pl = Xl + n * kFRows;            // [copy][kFRows] p
     double* red = Pl + n * kFRows;           // block_sum scratch
     if (a.done[bi] != 3) return;             // (monomorphic, or missing calls: the chip-wide path)
@@ -1114,14 +1170,30 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
         block_sum(sg2, red, tid);
         sig = sg2[0];
     }
-    // x to the block's global vectors (dbslmm_pcg_final reads it); each thread its own rows
+    // The sequence's results, straight from x in LDS (each thread its own rows; nothing reads the
+    // block's global x: dbslmm_pcg_final skips a block finished here): betas and status of its
+    // copies.  On a streamed run they go to the host's mirror too, and the (block, copy) flags
+    // are released at system scope after every thread's stores, so the host may copy this block
+    // out while the others still iterate.
 #pragma unroll
     for (int q = 0; q < kFPer; ++q) {
         const int i = tid + kThreads * q;
         if (i < m)
-            for (int c = 0; c < nx; ++c) a.X[(msh ? c : cc) * a.vstride + B.vo + i] = Xl[c * kFRows + i];
+            for (int c = 0; c < nx; ++c) put_beta(a, B, i, msh ? c : cc, Xl[c * kFRows + i], false);
     }
-    if (tid == 0) atomicMax(a.itb + bi, it + (it < maxit ? 1 : 0));   // (several copies: the slowest)
+    if (tid == 0) {
+        atomicMax(a.itb + bi, it + (it < maxit ? 1 : 0));   // (several copies: the slowest)
+        for (int c = 0; c < nx; ++c) put_status(a, B, msh ? c : cc, false);
+    }
+    if (a.mir_flag) {
+        // (the barrier orders every thread's stores before thread 0, whose system-scope release
+        // then publishes them with the flag: one L2 write-back per sequence, not one per wave)
+        __syncthreads();
+        if (tid == 0)
+            for (int c = 0; c < nx; ++c)
+                __hip_atomic_store(a.mir_flag + static_cast<int64_t>(bi) * n + (msh ? c : cc), a.run_no,
+                                   __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 extern "C" __global__ __launch_bounds__(pcg::kThreads)
@@ -1155,20 +1227,13 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_final(Pcg
     using namespace pcg;
     const int2 it = rows[blockIdx.x];
     const int bi = it.x, I = it.y, tid = threadIdx.x;
+    const int done = a.done[bi];
+    if (done == 3 || done == 1) return;      // solved whole (dbslmm_pcg_block) or converged on the chip-wide
+                                             // kernels (dbslmm_pcg_update): its results are written
     const PcgBlk B = a.blk[bi];
-    const bool mono = a.done[bi] == 2;
+    const bool mono = done == 2;
     const int r = tid & (kT - 1), h = tid >> 7, i = I * kT + r;
-    if (i < B.m) {
-        const int so = a.slot_out[B.row0 + i];
-        for (int k = h; k < a.ncopy; k += 2) {
-            const double bv = mono ? __builtin_nan("") : a.X[k * a.vstride + B.vo + i] * a.inv_sqrt_n;
-            if (so >= 0) a.beta_s[k * a.ns + so] = bv;
-            else a.beta_l[k * a.nl - 1 - so] = bv;
-        }
-    }
-    if (I == 0 && tid < a.ncopy) {
-        const int st = mono ? DBSLMM_BLOCK_MONOMORPHIC
-                            : a.cnv[B.sco + tid] == 0 ? DBSLMM_BLOCK_NOT_CONVERGED : DBSLMM_BLOCK_OK;
-        a.status[tid * a.nbk + a.blk_id[B.blk]] = st;
-    }
+    if (i < B.m)
+        for (int k = h; k < a.ncopy; k += 2) put_beta(a, B, i, k, a.X[k * a.vstride + B.vo + i], mono);
+    if (I == 0 && tid < a.ncopy) put_status(a, B, tid, mono);
 }

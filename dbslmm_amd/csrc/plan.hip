@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/dbslmm_hip.h"
+#include "out_ranges.hpp"
 
 // The kernels are compiled in this translation unit (no relocatable device code needed).
 #include "kernels.hip"
@@ -307,7 +308,7 @@ struct dbslmm_plan {
     std::vector<int32_t> h_pnseq;  // ... its sequences there (1, or the copies with large SNPs)
     bool pcg_join = false;         // the main stream still has to wait for dbslmm_pcg_block
     double *d_pvec = nullptr, *d_ppart = nullptr, *d_pdot = nullptr, *d_pqs = nullptr;
-    int32_t *d_pcnv = nullptr, *d_pitb = nullptr, *d_pdone = nullptr, *d_pact = nullptr;
+    int32_t *d_pcnv = nullptr, *d_pitb = nullptr, *d_pdone = nullptr, *d_pact = nullptr, *d_pfin = nullptr;
     int64_t pcg_vstride = 0;
     int32_t* h_pmon = nullptr;     // pinned: [active | itb per block] after a chunk
     int32_t pcg_it = 0;            // iterations enqueued by the current run
@@ -322,6 +323,23 @@ struct dbslmm_plan {
     double pcg_cbytes = 0.0, pcg_pbytes = 0.0, pcg_fbytes = 0.0;   // the latest run (workload [19]-[21])
     PcgArgs pcg_args{};            // the arguments of the latest PCG run (continuation chunks)
     hipEvent_t pcg_ev_end = nullptr;   // its timing end event (re-recorded by a continuation)
+    // ---- streamed results (dbslmm_options.stream_out): on the PCG route of dbslmm_plan_run_multi the
+    // kernels write every result to a host-visible mirror as well and flag each (route block, copy)
+    // they finish (dbslmm_pcg_block, dbslmm_pcg_update), and the calling thread copies flagged
+    // blocks into the caller's arrays while the GPU still iterates (stream_results)
+    bool stream_out = true;        // the option
+    bool so_want = false;          // the call in progress may stream (dbslmm_plan_run_multi)
+    bool so_active = false;        // the latest PCG run writes the mirror
+    void* h_mir = nullptr;         // pinned, mapped, coherent: [beta_s | beta_l | status], copy-major
+    size_t h_mir_bytes = 0;        //   (the layout and strides of the device arrays, so_n copies)
+    int32_t* h_mflag = nullptr;    // ... and [route block * so_n + copy] = so_run once finished
+    int32_t so_n = 0;              // copies of the latest streamed run
+    int32_t so_run = 0;            // its number (per plan; flags of earlier runs never match)
+    hipEvent_t so_ev = nullptr;    // after the last work a chunk enqueued
+    std::vector<OutRange> h_orange;   // per route block: its ranges of the caller's arrays
+    std::vector<int2> h_pfpairs;   // the host's scan order: dbslmm_pcg_block's (route block, copy) pairs in its
+                                   // list order, then the chip-wide blocks' 
+    std::vector<int32_t> so_done;  // [route block * so_n + copy] = so_run once copied out
 };
 
 #define HIP_TRY(ctx, expr)                                                               \
@@ -520,6 +538,36 @@ static void par_memcpy(void* dst, const void* src, size_t n) {
         if (a < z) th.emplace_back([=] { memcpy(static_cast<char*>(dst) + a, static_cast<const char*>(src) + a, z - a); });
     }
     memcpy(dst, src, std::min(n, part));
+    for (auto& t : th) t.join();
+}
+
+// The same for a list of copies (a streamed run's remainder: scattered block ranges), the bytes of
+// the concatenation split evenly over the threads.
+struct CopySeg {
+    void* dst;
+    const void* src;
+    size_t n;
+};
+static void par_memcpy_list(const std::vector<CopySeg>& segs) {
+    constexpr size_t kMin = size_t(512) << 10;
+    size_t total = 0;
+    for (const CopySeg& s : segs) total += s.n;
+    const unsigned hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    const unsigned nt = static_cast<unsigned>(std::min<size_t>(hw, std::max<size_t>(1, total / kMin)));
+    const size_t part = (total + nt - 1) / nt;
+    auto work = [&segs, part](unsigned t) {   // bytes [t part, (t + 1) part) of the concatenation
+        const size_t lo = t * part, hi = lo + part;
+        size_t off = 0;
+        for (const CopySeg& s : segs) {
+            const size_t a = std::max(lo, off), z = std::min(hi, off + s.n);
+            if (a < z) memcpy(static_cast<char*>(s.dst) + (a - off), static_cast<const char*>(s.src) + (a - off), z - a);
+            off += s.n;
+            if (off >= hi) break;
+        }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
+    work(0);
     for (auto& t : th) t.join();
 }
 
@@ -962,6 +1010,9 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
     (void)hipSetDevice(p->ctx->device);
     if (p->h_pin) (void)hipHostFree(p->h_pin);
     if (p->h_pmon) (void)hipHostFree(p->h_pmon);
+    if (p->h_mir) (void)hipHostFree(p->h_mir);
+    if (p->h_mflag) (void)hipHostFree(p->h_mflag);
+    if (p->so_ev) (void)hipEventDestroy(p->so_ev);
     p->img = PanelImage{};                      // (shared with the context when it came from its cache)
     void* bufs[] = {p->d_slot_pos, p->d_slot_block, p->d_slot_out, p->d_z,
                     p->d_S, p->d_mu, p->d_rsd, p->d_y, p->d_flags, p->d_status, p->d_order,
@@ -971,7 +1022,7 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
                     p->d_cheb, p->d_coef, p->d_stamps, p->d_tepi, p->d_cheb_items,
                     p->d_tcheb_blocks, p->d_cgrec, p->d_cgconv, p->d_cgit, p->d_G16, p->d_pblk,
                     p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
-                    p->d_pitb, p->d_pdone, p->d_pact, p->d_off16, p->d_ld16, p->d_pflist, p->d_pfnext};
+                    p->d_pitb, p->d_pdone, p->d_pact, p->d_off16, p->d_ld16, p->d_pflist, p->d_pfnext, p->d_pfin};
     for (void* b : bufs)
         if (b) {
             const hipError_t e = hipFree(b);
@@ -1029,9 +1080,11 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
                    (op.debug_stop == 0 || op.debug_stop == 1) && op.sub_split >= -1 && op.sub_split <= 2 &&
                    op.sub_grid_lead >= 0 && op.sub_grid_rest >= 0 && op.shard_copies >= 0 &&
                    op.shard_copies <= 64 && op.h2f_iter >= 0 && op.h2f_iter <= 2 && op.solver >= 0 &&
-                   op.solver <= 2 && op.pcg_tol >= 0.0 && op.pcg_maxit >= 0, "bad dbslmm_options");
+                   op.solver <= 2 && op.pcg_tol >= 0.0 && op.pcg_maxit >= 0 && op.stream_out >= -1 &&
+                   op.stream_out <= 1, "bad dbslmm_options");
     p->solver = op.solver;
     p->pcg_fused = op.pcg_whole >= 0;
+    p->stream_out = op.stream_out >= 0;
     if (op.pcg_tol > 0.0) p->pcg_tol = std::max(1e-15, op.pcg_tol);
     if (op.pcg_maxit > 0) p->pcg_maxit = op.pcg_maxit;
     p->pcg_g16 = 4 * static_cast<int64_t>(pr->n_ref) <= 65535;
@@ -1229,6 +1282,7 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     p->h_ld = ldv;
     p->h_blk_id = blk_id;
     p->h_matoff = matoff;
+    (void)build_out_ranges(pr->num_block, pr->s_ptr, has_l ? pr->l_ptr : nullptr, p->h_orange);   // (offsets checked above)
     // Cholesky work lists: large blocks (ld > 64, one workgroup each) then small blocks (one
     // wave each), each largest first (longest-processing-time order)
     std::vector<int32_t> order(p->n_nonempty);
@@ -2109,7 +2163,7 @@ static int pcg_layout(dbslmm_plan* p, int n) {
                                                hipHostMallocDefault));
     if (p->pcg_n == n) return DBSLMM_OK;
     void* old[] = {p->d_pblk, p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
-                   p->d_pitb, p->d_pdone, p->d_pact, p->d_pflist};
+                   p->d_pitb, p->d_pdone, p->d_pact, p->d_pflist, p->d_pfin};
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (void* q : old)
         if (q) (void)hipFree(q);
@@ -2179,6 +2233,14 @@ static int pcg_layout(dbslmm_plan* p, int n) {
         p->h_pnseq[f.x] += 1;
     }
     p->n_pflist = static_cast<int32_t>(flist.size());
+    // a streamed run's host scan: the (block, copy) pairs in the order dbslmm_pcg_block takes them,
+    // then those of the chip-wide blocks (flagged by dbslmm_pcg_update as each block converges)
+    p->h_pfpairs.clear();
+    for (const int2& f : flist)
+        for (int c = f.y < 0 ? 0 : f.y; c < (f.y < 0 ? n : f.y + 1); ++c) p->h_pfpairs.push_back(int2{f.x, c});
+    for (int b = 0; b < static_cast<int>(blk.size()); ++b)
+        if (!blk[b].fused)
+            for (int c = 0; c < n; ++c) p->h_pfpairs.push_back(int2{b, c});
     if (!flist.empty()) HIP_TRY(ctx, dev_upload(&p->d_pflist, flist, ctx->stream));
     if (!flist.empty() && !p->d_pfnext) HIP_TRY(ctx, hipMalloc(&p->d_pfnext, 16));
     p->n_pblk = static_cast<int32_t>(blk.size());
@@ -2198,6 +2260,7 @@ static int pcg_layout(dbslmm_plan* p, int n) {
     HIP_TRY(ctx, hipMalloc(&p->d_pitb, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
     HIP_TRY(ctx, hipMalloc(&p->d_pdone, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
     HIP_TRY(ctx, hipMalloc(&p->d_pact, sizeof(int32_t)));
+    HIP_TRY(ctx, hipMalloc(&p->d_pfin, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
     p->pcg_n = n;
     return DBSLMM_OK;
 }
@@ -2243,13 +2306,15 @@ static int pcg_iters(dbslmm_plan* p, int K) {
     HIP_TRY(ctx, hipMemcpyAsync(p->h_pmon, p->d_pact, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipMemcpyAsync(p->h_pmon + 1, p->d_pitb, p->n_pblk * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (p->pcg_ev_end) HIP_TRY(ctx, hipEventRecord(p->pcg_ev_end, s));
+    if (p->so_active) HIP_TRY(ctx, hipEventRecord(p->so_ev, s));   // (a streamed run polls it: stream_results)
     return DBSLMM_OK;
 }
 
-// Wait for a PCG run; while blocks still iterate (and the cap allows), enqueue further chunks.
-static int pcg_finish(dbslmm_plan* p) {
+// Wait for the latest chunk of a pending PCG run; while blocks still iterate (and the cap allows),
+// enqueue a further chunk (the run stays pending), else close the run.
+static int pcg_check(dbslmm_plan* p) {
     dbslmm_ctx* ctx = p->ctx;
-    while (p->pcg_pending) {
+    if (p->pcg_pending) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         int32_t need = 0;
@@ -2286,11 +2351,48 @@ static int pcg_finish(dbslmm_plan* p) {
                     p->pcg_pbytes += it * p->h_ppart[b];
                 }
             }
-            break;
+            return DBSLMM_OK;
         }
         const int K = std::min(std::max(4, p->pcg_it / 4), p->pcg_maxit - p->pcg_it);
         if (const int rc = pcg_iters(p, K)) return rc;
     }
+    return DBSLMM_OK;
+}
+
+// Wait for a PCG run, continuation chunks included.
+static int pcg_finish(dbslmm_plan* p) {
+    while (p->pcg_pending)
+        if (const int rc = pcg_check(p)) return rc;
+    return DBSLMM_OK;
+}
+
+// The mirror and flags of a streamed run of n copies, and its run number.
+static int so_prepare(dbslmm_plan* p, int n) {
+    dbslmm_ctx* ctx = p->ctx;
+    const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
+    const size_t bytes = static_cast<size_t>(n) * (p->n_s + p->n_l) * sizeof(double) +
+                         static_cast<size_t>(n) * p->nbk * sizeof(int32_t);
+    if (bytes > p->h_mir_bytes) {
+        if (p->h_mir) HIP_TRY(ctx, hipHostFree(p->h_mir));
+        p->h_mir = nullptr;
+        p->h_mir_bytes = 0;
+        HIP_TRY(ctx, hipHostMalloc(&p->h_mir, bytes, fl));
+        p->h_mir_bytes = bytes;
+    }
+    const size_t nf = static_cast<size_t>(std::max(1, p->n_nonempty)) * pcg::kMaxNC;
+    if (!p->h_mflag) {
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&p->h_mflag), nf * sizeof(int32_t), fl));
+        memset(p->h_mflag, 0, nf * sizeof(int32_t));
+        p->so_done.assign(nf, 0);
+    }
+    if (!p->so_ev) HIP_TRY(ctx, hipEventCreateWithFlags(&p->so_ev, hipEventDisableTiming));
+    if (p->so_run == INT32_MAX) {   // (no run in flight here: flags and marks restart with the numbers)
+        memset(p->h_mflag, 0, nf * sizeof(int32_t));
+        p->so_done.assign(nf, 0);
+        p->so_run = 0;
+    }
+    p->so_run++;
+    p->so_n = n;
     return DBSLMM_OK;
 }
 
@@ -2318,6 +2420,10 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
         if (e != hipSuccess) fprintf(stderr, "run_pcg: error after pcg_layout: %s\n", hipGetErrorString(e));
     }
 #endif
+    // results streamed to the host while the run iterates: dbslmm_plan_run_multi on one device
+    p->so_active = p->so_want && p->stream_out;
+    if (p->so_active)
+        if (const int rc = so_prepare(p, n)) return rc;
     hipStream_t s = ctx->stream;
     hipEvent_t* ev = nullptr;
     if (p->timing) {
@@ -2401,9 +2507,20 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     a.itb = p->d_pitb;
     a.done = p->d_pdone;
     a.active = p->d_pact;
+    a.fin = p->d_pfin;
     a.beta_s = p->d_beta_s;
     a.beta_l = p->d_beta_l;
     a.status = p->d_status;
+    if (p->so_active) {   // the mirror through its device addresses: [beta_s | beta_l | status]
+        void *dm = nullptr, *df = nullptr;
+        HIP_TRY(ctx, hipHostGetDevicePointer(&dm, p->h_mir, 0));
+        HIP_TRY(ctx, hipHostGetDevicePointer(&df, p->h_mflag, 0));
+        a.mir_s = static_cast<double*>(dm);
+        a.mir_l = a.mir_s + static_cast<int64_t>(n) * p->n_s;
+        a.mir_st = reinterpret_cast<int32_t*>(a.mir_l + static_cast<int64_t>(n) * p->n_l);
+        a.mir_flag = static_cast<int32_t*>(df);
+        a.run_no = p->so_run;
+    }
     a.vstride = p->pcg_vstride;
     a.ns = p->n_s;
     a.nl = p->n_l;
@@ -2837,6 +2954,83 @@ static int download_copies(dbslmm_plan* p, int c0, int n, double* beta_s, double
     return DBSLMM_OK;
 }
 
+// The results of a streamed PCG run (run_pcg with so_active) into the caller's arrays, from the
+// plan's host-visible mirror and without a download: while the run's latest chunk is on the GPU
+// the calling thread polls its end event and copies out every (route block, copy) flagged since
+// the last look (by dbslmm_pcg_block at the end of a sequence, by dbslmm_pcg_update when a
+// chip-wide block has converged) -- that block's range of beta_s, its few beta_l entries and its
+// status -- so nearly all the bytes have left before the last kernel ends.  The flags only say
+// what may be copied early; once the run is over, whatever was not copied (monomorphic blocks and
+// blocks at the iteration cap, which dbslmm_pcg_final writes, and any block whose flag was not
+// seen in time) is copied regardless of them, so no result can be missed and nothing waits on a
+// flag.  Timing events are collected after the copy-out.
+static int stream_results(dbslmm_plan* p, double* beta_s, double* beta_l, int32_t* block_status) {
+    dbslmm_ctx* ctx = p->ctx;
+    const int n = p->so_n;
+    const int32_t run = p->so_run;
+    const double* ms = static_cast<const double*>(p->h_mir);
+    const double* ml = ms + static_cast<int64_t>(n) * p->n_s;
+    const int32_t* mst = reinterpret_cast<const int32_t*>(ml + static_cast<int64_t>(n) * p->n_l);
+    if (!p->num_block) block_status = nullptr;
+    auto copy_out = [&](int b, int c) {
+        const OutRange& r = p->h_orange[b];
+        if (beta_s && r.s1 > r.s0)
+            memcpy(beta_s + c * p->n_s + r.s0, ms + c * p->n_s + r.s0, (r.s1 - r.s0) * sizeof(double));
+        if (beta_l && r.l1 > r.l0)
+            memcpy(beta_l + c * p->n_l + r.l0, ml + c * p->n_l + r.l0, (r.l1 - r.l0) * sizeof(double));
+        if (block_status) block_status[static_cast<int64_t>(c) * p->num_block + r.blk] = mst[c * p->nbk + r.blk];
+        p->so_done[static_cast<size_t>(b) * n + c] = run;
+    };
+    const std::vector<int2>& pairs = p->h_pfpairs;
+    size_t head = 0;                         // every pair before it is copied
+    bool polled = false;
+    while (p->pcg_pending) {
+        for (;;) {
+            const hipError_t q = hipEventQuery(p->so_ev);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) HIP_TRY(ctx, q);
+            polled = true;
+            for (size_t e = head; e < pairs.size(); ++e) {
+                const size_t f = static_cast<size_t>(pairs[e].x) * n + pairs[e].y;
+                if (p->so_done[f] != run && __atomic_load_n(p->h_mflag + f, __ATOMIC_ACQUIRE) == run)
+                    copy_out(pairs[e].x, pairs[e].y);
+            }
+            while (head < pairs.size() && p->so_done[static_cast<size_t>(pairs[head].x) * n + pairs[head].y] == run)
+                ++head;
+        }
+        if (const int rc = pcg_check(p)) return rc;   // (may enqueue another chunk: poll again)
+    }
+    if (polled) (void)hipGetLastError();     // (hipErrorNotReady of the polls is no error)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = check_trsv(p)) return rc;
+    // the rest: runs of neighbouring blocks not copied yet are one range of beta_s / beta_l each
+    std::vector<CopySeg> rest;
+    for (int c = 0; c < n; ++c)
+        for (int b = 0; b < p->n_pblk;) {
+            if (p->so_done[static_cast<size_t>(b) * n + c] == run) { ++b; continue; }
+            int e = b;
+            while (e + 1 < p->n_pblk && p->so_done[static_cast<size_t>(e + 1) * n + c] != run) ++e;
+            const OutRange &r0 = p->h_orange[b], &r1 = p->h_orange[e];
+            if (beta_s && r1.s1 > r0.s0)
+                rest.push_back({beta_s + c * p->n_s + r0.s0, ms + c * p->n_s + r0.s0, (r1.s1 - r0.s0) * sizeof(double)});
+            if (beta_l && r1.l1 > r0.l0)
+                rest.push_back({beta_l + c * p->n_l + r0.l0, ml + c * p->n_l + r0.l0, (r1.l1 - r0.l0) * sizeof(double)});
+            for (int k = b; k <= e; ++k) {
+                const int32_t id = p->h_orange[k].blk;
+                if (block_status) block_status[static_cast<int64_t>(c) * p->num_block + id] = mst[c * p->nbk + id];
+                p->so_done[static_cast<size_t>(k) * n + c] = run;
+            }
+            b = e + 1;
+        }
+    par_memcpy_list(rest);
+    for (int c = 0; c < n && block_status; ++c)
+        for (int32_t b : p->h_empty) block_status[static_cast<int64_t>(c) * p->num_block + b] = DBSLMM_BLOCK_EMPTY;
+    if (p->timing) return collect_timing(p);
+    p->runs_pending = 0;
+    p->run_route.clear();
+    return DBSLMM_OK;
+}
+
 static int download_copy(dbslmm_plan* p, int c, double* beta_s, double* beta_l, int32_t* block_status) {
     return download_copies(p, c, 1, beta_s, beta_l, block_status);
 }
@@ -2866,7 +3060,10 @@ int dbslmm_plan_run_multi(dbslmm_plan* p, const double* sigmas, int32_t n_sigma,
     }
     ARG_CHECK(ctx, static_cast<int64_t>(p->n_nonempty) * n_sigma < 32768,
               "blocks x sigmas must stay below 32768 (packed work items)");
+    p->so_want = true;                       // (the PCG route may stream its results: stream_out)
     int rc = run_impl(p, true, sigmas, n_sigma);
+    p->so_want = false;
+    if (!rc && p->pcg_ran && p->so_active) return stream_results(p, beta_s, beta_l, block_status);
     if (!rc) rc = dbslmm_plan_sync(p);
     if (!rc) rc = download_copies(p, 0, n_sigma, beta_s, beta_l, block_status);
     return rc;
@@ -2925,6 +3122,19 @@ int dbslmm_plan_block_iters(dbslmm_plan* p, int32_t* iters) {
     std::fill(iters, iters + p->num_block, 0);
     if (!p->pcg_ran) return DBSLMM_OK;
     for (int b = 0; b < p->n_pblk; ++b) iters[p->h_blk_id[b]] = p->h_pmon[1 + b];
+    return DBSLMM_OK;
+}
+
+int dbslmm_out_ranges(int32_t num_block, const int64_t* s_ptr, const int64_t* l_ptr, int64_t* ranges,
+                      int32_t* n_ranges) {
+    if (num_block < 0 || !s_ptr || !ranges || !n_ranges) return DBSLMM_E_ARG;
+    std::vector<OutRange> t;
+    if (!build_out_ranges(num_block, s_ptr, l_ptr, t)) return DBSLMM_E_ARG;
+    for (size_t i = 0; i < t.size(); ++i) {
+        const int64_t row[5] = {t[i].blk, t[i].s0, t[i].s1, t[i].l0, t[i].l1};
+        std::copy(row, row + 5, ranges + 5 * i);
+    }
+    *n_ranges = static_cast<int32_t>(t.size());
     return DBSLMM_OK;
 }
 

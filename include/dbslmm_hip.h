@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 16
+#define DBSLMM_ABI_VERSION 17
 
 enum {
     DBSLMM_OK = 0,
@@ -142,6 +142,16 @@ typedef struct dbslmm_plan dbslmm_plan;
  *                solved whole by one workgroup per Krylov sequence (dbslmm_pcg_block) beside the
  *                chip-wide iterations of the others; 0 = default (on), -1 = off (every block on
  *                the chip-wide kernels: A/B and parity tests).  Results agree within pcg_tol.
+ * stream_out     PCG route of dbslmm_plan_run_multi on one device (ABI 17): 1 (and 0, the default)
+ *                = the kernels write every result to a host-visible pinned mirror as well as the
+ *                device arrays and flag each block they finish (dbslmm_pcg_block at the end of a
+ *                sequence, dbslmm_pcg_update when a chip-wide block has converged), and the calling
+ *                thread copies finished blocks into the caller's arrays while the GPU still
+ *                iterates (no device-to-host copy after the last kernel); -1 = off: the run is
+ *                waited for and downloaded through the pinned staging buffer, as the
+ *                factorisation route, plan_run + plan_download and multi-device contexts always
+ *                are.  Bit-identical results either way.  (The Python binding passes an explicit
+ *                stream_out = 0 as -1, so there 1 / 0 read on / off.)
  */
 typedef struct dbslmm_options {
     int32_t tiled_min;
@@ -163,6 +173,7 @@ typedef struct dbslmm_options {
     double pcg_tol;
     int32_t pcg_maxit;
     int32_t pcg_whole;
+    int32_t stream_out;
 } dbslmm_options;
 
 /* One LD-block problem set, the arguments of DBSLMMFIT::est in flat form.
@@ -355,6 +366,15 @@ int dbslmm_plan_workload(const dbslmm_plan* plan, double* out /*[DBSLMM_WORKLOAD
  * iterations block b ran before its every copy met the stopping rule (pcg_maxit at the cap), 0 for
  * empty blocks and after a run on the factorisation route.  Waits for the run. */
 int dbslmm_plan_block_iters(dbslmm_plan* plan, int32_t* iters);
+
+/* Where each block's results lie in the caller's arrays (ABI 17; tests and diagnostics, host only:
+ * no context, no GPU): the table a streamed run (dbslmm_options.stream_out) copies finished blocks
+ * out by.  ranges receives one row of 5 per non-empty block, in block order -- {block, s0, s1, l0,
+ * l1}: beta_s[s0 .. s1), beta_l[l0 .. l1) and status entry `block` -- and has room for num_block
+ * rows; *n_ranges their number.  l_ptr NULL: no large SNPs.  DBSLMM_E_ARG when the offsets are not
+ * monotone. */
+int dbslmm_out_ranges(int32_t num_block, const int64_t* s_ptr, const int64_t* l_ptr, int64_t* ranges,
+                      int32_t* n_ranges);
 
 /* Diagnostics (parity tests): after plan_sync, the working matrix of block `block` (original
  * block id) in factorisation copy `copy`: ld x ld fp64, row-major, ld = *ld_out (out == NULL:
