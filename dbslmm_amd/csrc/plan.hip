@@ -242,6 +242,7 @@ struct dbslmm_plan {
     int32_t tiled_min = 0;                   // blocks with m >= this are on the tiled path
     int32_t h2f_mode = 0;                    // dbslmm_options.h2f_mode
     double cheb_tol = 1e-9;                  // dbslmm_options.cheb_tol
+    double h2f_tol = 1e-9;                   // the current run's target for its iterated copies (run_impl)
     bool large_cheb_ok = true;               // dbslmm_options.large_cheb and every chol_large block
                                              // fits dbslmm_chol_cheb (ld <= chol::kChebMaxM)
     bool cheb_fused = false;                 // dbslmm_options.cheb_fused
@@ -1783,7 +1784,7 @@ static bool cheb_plan(const dbslmm_plan* p, const double* sigmas, int n, ChebPla
     const double db = 1.0 / (sigmas[cp.base] * nobs);
     cp.db = db;
     const double floor_ = db + 1.0 - p->tau;
-    const double tol = p->cheb_tol;
+    const double tol = p->h2f_tol;
     for (int c = 0; c < n; ++c)
         if (c != cp.base) cp.others.push_back(c);
     for (size_t g0 = 0; g0 < cp.others.size(); g0 += trsv::kMaxR) {
@@ -2020,7 +2021,7 @@ static int run_cheb(dbslmm_plan* p, double isn, const ChebPlan& cp, const TGroup
                     ca.cix[j] = cix[j];
                 }
                 ca.floor_l = 1.0 - p->tau;
-                ca.tol = p->cheb_tol;
+                ca.tol = p->h2f_tol;
                 ca.rec = p->d_cgrec;
                 ca.conv = p->d_cgconv;
                 ca.iters = p->d_cgit;
@@ -2126,13 +2127,17 @@ static int run_tcheb(dbslmm_plan* p, double isn, const ChebPlan& cp, hipStream_t
 // lower bound on lambda_min (tau < 1, or no large SNPs: then d_c + 1 - tau), at most
 // pcg::kMaxNC copies and no debug stop after the Gram.
 constexpr double kPcgDmin = 2.0;
-static bool pcg_route(const dbslmm_plan* p, const double* sigmas, int n) {
+// ... every condition but the number of copies
+static bool pcg_eligible(const dbslmm_plan* p, const double* sigmas, int n) {
     if (p->force_factor || p->solver == 1 || p->n_nonempty == 0 || p->debug_stop) return false;
-    if (n > pcg::kMaxNC || !(p->tau > 0.0 && p->tau <= 1.0) || (p->tau >= 1.0 && p->has_large)) return false;
+    if (!(p->tau > 0.0 && p->tau <= 1.0) || (p->tau >= 1.0 && p->has_large)) return false;
     if (p->solver == 2) return true;
     for (int c = 0; c < n; ++c)
         if (1.0 / (sigmas[c] * static_cast<double>(p->n_obs)) < kPcgDmin) return false;
     return true;
+}
+static bool pcg_route(const dbslmm_plan* p, const double* sigmas, int n) {
+    return n <= pcg::kMaxNC && pcg_eligible(p, sigmas, n);
 }
 
 // Lay the PCG buffers out for n copies: per block its tile rows (128 slots), the product's work
@@ -2583,6 +2588,11 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (const int rc = pcg_finish(p)) return rc;   // a PCG run still pending (plan_run without sync)
     if (front && pcg_route(p, sigmas, n)) return run_pcg(p, sigmas, n);
+    // A run kept off the PCG route by its number of copies alone keeps that route's accuracy: its
+    // iterated h2f copies stop at pcg_tol (relative error per block and copy, as run_pcg), so a
+    // fifth h2f factor does not move the results of the others from 1e-12 to cheb_tol.
+    p->h2f_tol = front && n > pcg::kMaxNC && pcg_eligible(p, sigmas, n) ? std::min(p->cheb_tol, p->pcg_tol)
+                                                                         : p->cheb_tol;
     if (const int rc = ensure_copies(p, n, n)) return rc;
     if (n > 1) {
         if (p->multi_n != n) {
@@ -2760,7 +2770,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                 cgs.on = p->h2f_cg ? 1 : 0;
                 for (int j = 0; j < nr; ++j) cgs.fs[j] = cp.db + cp.coef[cp.coef_off[g] + 3 * j + 2] + 1.0 - p->tau;
                 cgs.fl = 1.0 - p->tau;
-                cgs.tol = p->cheb_tol;
+                cgs.tol = p->h2f_tol;
                 hipLaunchKernelGGL(dbslmm_chol_cheb, dim3(p->n_large), dim3(chol::kChebThreads), kCholChebLds, s,
                                    p->d_M + bc * p->M_elems, p->d_order, p->n_large, p->d_row0, p->d_m, p->d_ms,
                                    p->d_ld, p->d_matoff, p->d_blk_id, p->d_slot_out, p->d_y + bc * p->n_slots,

@@ -75,7 +75,9 @@ typedef struct dbslmm_plan dbslmm_plan;
  *                own deviation from the exact solution (~1e-8)).  CG (the default h2f_iter) stops a
  *                block once |r| <= cheb_tol lambda_min(M_c) |x| (5.03 iterations per tiled block at
  *                config 4); Chebyshev runs its a priori count (7 at h2f 0.8 / 1 / 1.2), which is
- *                also CG's cap
+ *                also CG's cap.  A run that only its number of sigmas (more than 4) keeps off the PCG
+ *                route (solver 2, or solver 0 with every 1/(sigma n) >= 2) uses pcg_tol instead, so
+ *                its results stay as accurate as those of a run of up to 4 sigmas
  * lead_min       tiled blocks with m >= lead_min form the lead group: their Gram tiles run first
  *                and their factorisation (the longest dependency chains) starts right after
  *                them, beside the rest of the Gram and the other blocks' factorisation (default

@@ -110,3 +110,120 @@ def rows_close(a: str, b: str, ulps: int = 1) -> bool:
         if abs(fx - fy) > ulps * scale * 1.0000001:
             return False
     return True
+
+
+# ----------------------------------------------------------------------------- PCG-route panels
+# One block of each kind the PCG route treats differently (pcg.hip): whole-block multi-shift blocks
+# without large SNPs (70, 600), a whole-block block with large SNPs (200), chip-wide blocks (more
+# than 1024 slots) without and with large SNPs (1030, 1100), an empty block, a block under 64 SNPs.
+PCG_SIZES = (70, 600, 200, 1030, 1100, 0, 40)
+PCG_LARGE = (0, 0, 2, 0, 3, 0, 0)
+
+
+class PcgCase:
+    """prob (a fresh BlockProblem), the matching test panel (tbed, ind) and the test rows of the
+    small / large SNPs (ts_pos, tl_pos; permuted), sizes."""
+
+
+_PANELS = {}
+
+
+def _pcg_panels(total, n_ref, n_total, seed):
+    from dbslmm_amd import synth
+    key = (total, n_ref, n_total, seed)
+    if key not in _PANELS:
+        p = synth.simulate(total + 50, n_ref, pop="EUR", chroms=[1, 2], seed=seed, miss_rate=0.0, large_every=0)
+        t = synth.simulate(total + 50, n_total, pop="EUR", chroms=[1, 2], seed=seed + 100, miss_rate=0.0,
+                           large_every=0)
+        _PANELS[key] = (p.bed, t.bed)
+    return _PANELS[key]
+
+
+def pcg_case(sizes=PCG_SIZES, n_large=PCG_LARGE, n_ref=128, n_obs=100000, sigma_s=0.5 / 1e6, tau=0.8,
+             lmm=False, miss_block=None, mono_block=None, zero_blocks=(), n_total=150, seed=5, **opts):
+    """Blocks of sizes[b] SNPs (0: an empty block), the first n_large[b] of each large (z = +-6).
+    The defaults give a prior shift 1 / (sigma_s n_obs) = 20, as the flagship configurations: the
+    auto rule takes the PCG route with no solver option.  miss_block gets one missing call (its
+    products then read the fp64 Sigma and the whole-block kernel hands it back), mono_block one
+    zero-variance SNP, zero_blocks a right-hand side that is exactly zero; lmm: the large SNPs
+    stay small ones (LMM-only, no l_ptr).  The test panel holds the same SNPs at permuted rows."""
+    from dbslmm_amd import BlockProblem
+    sizes, n_large = np.asarray(sizes), np.asarray(n_large)
+    total = int(sizes.sum())
+    ref_bed, test_bed = _pcg_panels(total, n_ref, n_total, seed)
+    bed = ref_bed.copy()
+    rng = np.random.default_rng(seed)
+    bid = np.repeat(np.arange(len(sizes)), sizes)
+    first = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+    large = (np.arange(total) - first[bid]) < n_large[bid]
+    z = rng.standard_normal(total)
+    z[large] = 6.0 * np.sign(z[large])
+    for b in zero_blocks:
+        z[bid == b] = 0.0
+    if lmm:
+        large[:] = False
+    nb = (n_ref + 3) // 4
+    if miss_block is not None:
+        j = int(first[miss_block]) + 3
+        bed[3 + j * nb] = (bed[3 + j * nb] & 0xFC) | 0x01          # PLINK code 01: a missing call
+    if mono_block is not None:
+        j = int(first[mono_block]) + 5
+        bed[3 + j * nb: 3 + (j + 1) * nb] = 0xFF                   # every call homozygous: zero variance
+
+    def csr(mask):
+        idx = np.flatnonzero(mask)
+        ptr = np.zeros(len(sizes) + 1, dtype=np.int64)
+        np.add.at(ptr, bid[idx] + 1, 1)
+        return np.cumsum(ptr), idx.astype(np.int32), z[idx]
+    s_ptr, s_pos, z_s = csr(~large)
+    kw = {}
+    if not lmm:
+        l_ptr, l_pos, z_l = csr(large)
+        kw = dict(l_ptr=l_ptr, l_pos=l_pos, z_l=z_l)
+    c = PcgCase()
+    c.prob = BlockProblem(bed=bed, n_ref=n_ref, n_obs=n_obs, sigma_s=sigma_s, tau=tau, s_ptr=s_ptr, s_pos=s_pos,
+                          z_s=z_s, opts=dict(opts), **kw)
+    c.sizes = sizes
+    # the test panel: SNP r sits at test row perm[r]
+    rows = total + 50
+    perm = rng.permutation(rows).astype(np.int32)
+    tb = (n_total + 3) // 4
+    c.tbed = np.zeros(3 + rows * tb, dtype=np.uint8)
+    c.tbed[:3] = test_bed[:3]
+    c.tbed[3:].reshape(rows, tb)[perm] = test_bed[3:].reshape(rows, tb)
+    c.ind = (rng.random(n_total) < 0.75).astype(np.int32)
+    c.ts_pos = perm[s_pos]
+    c.tl_pos = None if lmm else perm[l_pos]
+    return c
+
+
+def blockwise(prob, got, ref, skip=()):
+    """The per-block bar: the worst over the blocks of max |got - ref| / max |ref| on the joint
+    vector [beta_s of the block | beta_l of the block]; got / ref are (beta_s, beta_l) pairs or
+    their concatenation.  A block whose reference is not finite (the oracle's 0/0 column of a
+    monomorphic SNP) or that is listed in skip is left to the caller."""
+    def pair(x):
+        if isinstance(x, (tuple, list)):
+            return np.asarray(x[0]), np.asarray(x[1])
+        x = np.asarray(x)
+        return x[:prob.n_s], x[prob.n_s:]
+    (gs, gl), (rs, rl) = pair(got), pair(ref)
+    assert gs.shape == rs.shape == (prob.n_s,) and gl.shape == rl.shape == (prob.n_l,)
+    worst = 0.0
+    for b in range(prob.num_block):
+        s = slice(prob.s_ptr[b], prob.s_ptr[b + 1])
+        g, r = gs[s], rs[s]
+        if prob.l_ptr is not None:
+            l = slice(prob.l_ptr[b], prob.l_ptr[b + 1])
+            g, r = np.concatenate([g, gl[l]]), np.concatenate([r, rl[l]])
+        if r.size == 0 or b in skip or not np.all(np.isfinite(r)):
+            continue
+        scale = np.max(np.abs(r))
+        if scale == 0.0:
+            assert np.all(g == 0.0), b
+            continue
+        err = float(np.max(np.abs(g - r)) / scale)
+        if not np.isfinite(err):                                   # (max() would drop a NaN)
+            return float("inf")
+        worst = max(worst, err)
+    return worst

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from _common import GOLD, normwise, synth_small_problem, td_problem
+from _common import GOLD, blockwise, normwise, pcg_case, synth_small_problem, td_problem
 from test_tiled import _oracle, _problem
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +54,17 @@ def _ok(st, d):
     return bool(np.all(np.where(m > 0, st == 0, st == 1)))
 
 
+def _per_block(prob, got, ref, what, skip=()):
+    """The per-block bar (_common.blockwise): per block the joint vector [beta_s of the block |
+    beta_l of the block] against the oracle, max |dbeta| / max |beta_block| <= 1e-10.  Large SNPs
+    (z = 6, no shift) have betas about 100 times the small ones', so under the one normwise() over
+    all blocks a block without large SNPs could be wrong at 1e-8 of its own scale."""
+    err = blockwise(prob, got, ref, skip=skip)
+    print(f"{what}: worst block vs oracle {err:.3e}")
+    assert err <= 1e-10, (what, err)
+    return err
+
+
 @pytest.mark.parametrize("lmm", [False, True], ids=["dbslmm", "lmm"])
 def test_testdat_forced_pcg_matches_oracle_and_golden(lmm):
     """test_dat (the reference's example, one block of 716 SNPs, cond ~124): the auto rule keeps it
@@ -86,6 +97,7 @@ def test_missing_calls_take_the_fp64_sigma():
         ok = np.isfinite(ref)
         assert np.array_equal(np.isfinite(got), ok)
         assert normwise(got[ok], ref[ok]) < 1e-10
+        _per_block(_prob(d), got, ref, f"synth_small lmm={lmm}")
 
 
 @pytest.mark.parametrize("factors", [(1.0,), (0.8, 1.0, 1.2), (0.5, 0.8, 1.0, 1.3)])
@@ -114,6 +126,7 @@ def test_auto_pcg_h2f_matches_factorisation(factors):
     a = _cat(pc[-1])
     ok = np.isfinite(ref) & np.isfinite(a)     # (the oracle's 0/0 column of the monomorphic block)
     assert normwise(a[ok], ref[ok]) < 1e-10
+    _per_block(prob, a, ref, f"auto h2f {factors}", skip=(4,))
 
 
 def test_pcg_repeatable_and_equal_to_single_copy_runs():
@@ -179,6 +192,7 @@ def test_large_panel_fp64_sigma_path():
     assert wl["pcg_route"] == 1
     ref, _ = _oracle(prob)
     assert normwise(_cat(res), ref) < 1e-10
+    _per_block(prob, _cat(res), ref, "n_ref 16500")
     assert np.all(res[2] == 0)
 
 
@@ -210,6 +224,7 @@ def test_whole_block_kernel_matches_chip_path(factors):
     a = _cat(fz[-1])
     ok = np.isfinite(ref) & np.isfinite(a)
     assert normwise(a[ok], ref[ok]) < 1e-10
+    _per_block(prob, a, ref, f"whole-block kernel {factors}", skip=(4,))
 
 
 def test_block_sizes_at_the_quadrant_and_whole_block_edges():
@@ -234,4 +249,112 @@ def test_block_sizes_at_the_quadrant_and_whole_block_edges():
         prob.sigma_s = s
         ref, _ = _oracle(prob)
         assert normwise(_cat(fz[c]), ref) < 1e-10, (c, normwise(_cat(fz[c]), ref))
+        _per_block(prob, _cat(fz[c]), ref, f"block-size edges, copy {c}")
+        _per_block(prob, _cat(ch[c]), ref, f"block-size edges, chip-wide path, copy {c}")
     prob.sigma_s = base
+
+
+def _oracle_at(prob, sigma):
+    base = prob.sigma_s
+    prob.sigma_s = sigma
+    ref, _ = _oracle(prob)
+    prob.sigma_s = base
+    return ref
+
+
+ZERO_SIZES, ZERO_LARGE, ZERO_BLOCKS = (150, 64, 200, 300, 1030, 1100), (0, 0, 1, 2, 0, 1), (1, 2, 4, 5)
+
+
+@pytest.mark.parametrize("factors", [(1.0,), (0.8, 1.0, 1.2)], ids=["1copy", "3copies"])
+def test_zero_right_hand_side_blocks_stay_exactly_zero(factors):
+    """Blocks whose z is exactly 0 -- 64 SNPs and 1030 SNPs without large SNPs (whole-block and
+    chip-wide multi-shift sequences), 200 and 1100 SNPs with a large SNP (per-copy sequences) --
+    beside normal blocks.  At iteration 0 gamma / delta is 0 / 0; only the rr == 0.0 test of
+    dbslmm_pcg_update and dbslmm_pcg_block keeps it out of x.  Status OK, every beta of those
+    blocks == 0 (-0.0 passes), nothing NaN, the other blocks within the parity bar of the oracle,
+    a second run bit-identical."""
+    c = pcg_case(sizes=ZERO_SIZES, n_large=ZERO_LARGE, zero_blocks=ZERO_BLOCKS)
+    prob = c.prob
+    sig = [prob.sigma_s * f for f in factors]
+    a, wl = _run(prob, sig)
+    b, _ = _run(prob, sig)
+    assert wl["pcg_route"] == 1
+    for k, s in enumerate(sig):
+        bs, bl, st = a[k]
+        assert np.all(st == 0), st
+        assert not np.any(np.isnan(bs)) and not np.any(np.isnan(bl))
+        for blk in ZERO_BLOCKS:
+            assert np.all(bs[prob.s_ptr[blk]:prob.s_ptr[blk + 1]] == 0), (k, blk)
+            assert np.all(bl[prob.l_ptr[blk]:prob.l_ptr[blk + 1]] == 0), (k, blk)
+        ref = _oracle_at(prob, s)
+        _per_block(prob, _cat(a[k]), ref, f"zero right-hand sides, copy {k}", skip=ZERO_BLOCKS)
+        assert all(np.array_equal(u, v) for u, v in zip(a[k], b[k]))
+
+
+@pytest.mark.parametrize("factors", [(1.0,), (0.8, 1.0, 1.2)], ids=["1copy", "3copies"])
+def test_tau_one_lmm_only_takes_the_pcg_route(factors):
+    """tau = 1 without large SNPs: lambda_min >= d alone, the (1 - tau) u term of the product
+    vanishes and Sigma is singular for every block of m > n_ref = 128 (600, 1030, 1100 SNPs here);
+    the auto rule still takes PCG (d = 20).  Per-block parity with the oracle at tau = 1."""
+    prob = pcg_case(lmm=True, tau=1.0).prob
+    assert np.diff(prob.s_ptr).max() > prob.n_ref
+    sig = [prob.sigma_s * f for f in factors]
+    out, wl = _run(prob, sig)
+    assert wl["pcg_route"] == 1
+    for k, s in enumerate(sig):
+        assert _ok(out[k][2], dict(s_ptr=prob.s_ptr))
+        _per_block(prob, _cat(out[k]), _oracle_at(prob, s), f"tau = 1 LMM-only, copy {k}")
+
+
+def test_tau_one_testdat_lmm_forced_pcg_matches_golden():
+    """test_dat LMM-only as the Manual runs it (tau = 1, nsnp = 998), forced onto PCG."""
+    d = td_problem(lmm_only=True, nsnp=998, tau=1.0)
+    (res,), wl = _run(_prob(d, solver=2))
+    assert wl["pcg_route"] == 1 and _ok(res[2], d)
+    got = _cat(res)
+    gd, gp = GOLDEN["lmm_tau1.0_nsnp998_direct"], GOLDEN["lmm_tau1.0_nsnp998_pcg"]
+    ref = np.concatenate([gd["beta_s"], gd["beta_l"]])
+    _per_block(_prob(d), got, ref, "test_dat LMM-only tau = 1")       # (one block: the normwise bar)
+    assert normwise(got, np.concatenate([gp["beta_s"], gp["beta_l"]])) < 1e-5
+
+
+def test_route_rule_edges_on_the_gpu():
+    """The edges of pcg_route() (test_pcg_paths.rule_cases): d exactly 2.0 takes PCG, the next fp64
+    sigma the factorisation; 5 copies (more than kMaxNC) and tau = 1 with large SNPs fall to the
+    factorisation even under solver = 2; tau = 1 LMM-only and 4 copies take PCG.  Every result is
+    within the parity bar of the oracle, and dist.shard_units_problem decides as the plan did."""
+    from test_pcg_paths import check_shard_rule, rule_cases
+    for name, prob, sig, route in rule_cases():
+        out, wl = _run(prob, sig)
+        assert wl["pcg_route"] == route, (name, wl["pcg_route"])
+        check_shard_rule(prob, sig, int(wl["pcg_route"]))
+        for k, s in enumerate(sig):
+            assert _ok(out[k][2], dict(s_ptr=prob.s_ptr, l_ptr=prob.l_ptr)), name
+            _per_block(prob, _cat(out[k]), _oracle_at(prob, s), f"rule edge {name}, copy {k}")
+
+
+def test_five_copies_under_solver_2_fall_to_the_factorisation():
+    """More than pcg::kMaxNC = 4 copies with solver = 2 (and under the auto rule at d = 20) and the
+    default h2f mode: pcg_route == 0, dist.shard_units_problem decides the same, statuses OK, and
+    every copy is held to the parity bar per block (1e-10) against the oracle's direct solve.
+
+    On the factorisation route only the base copy (the median sigma) is factored; the others
+    iterate on its factor.  Their default target cheb_tol = 1e-9 missed this bar (worst block per
+    copy at sigma factors 0.6 / 0.8 / 1.0 / 1.2 / 1.4: 3.05e-10, 1.47e-12, 2.93e-15 for the base
+    copy, 9.00e-12, 4.45e-10): adding a fifth h2f factor moved the results of a PCG-route problem
+    from pcg_tol to cheb_tol.  run_impl now holds a run that only its copy count keeps off the PCG
+    route to pcg_tol (plan.hip: h2f_tol); measured values: DESIGN.md section 4."""
+    from test_pcg_paths import FIVE, check_shard_rule, five_copies_case
+    forced, sig = five_copies_case()
+    auto = pcg_case(sizes=(70, 300, 200, 1030, 0, 40), n_large=(0, 0, 2, 1, 0, 0)).prob
+    assert forced.opts == {"solver": 2} and auto.opts == {} and len(sig) == len(FIVE) == 5
+    for name, prob in (("solver = 2", forced), ("auto", auto)):
+        out, wl = _run(prob, sig)
+        assert wl["pcg_route"] == 0 and wl["cheb_iters"] > 0, name      # (iterated, not merged)
+        check_shard_rule(prob, sig, 0)
+        errs = []
+        for k, s in enumerate(sig):
+            assert _ok(out[k][2], dict(s_ptr=prob.s_ptr, l_ptr=prob.l_ptr)), k
+            errs.append(blockwise(prob, _cat(out[k]), _oracle_at(prob, s)))
+        print(f"five copies, {name}: worst block vs oracle per copy", " ".join(f"{e:.3e}" for e in errs))
+        assert max(errs) <= 1e-10, (name, errs)

@@ -56,6 +56,25 @@ def test_factor_form_equals_literal_formulas(ml):
     assert np.max(np.abs(got - lit)) / np.max(np.abs(lit)) < 1e-12
 
 
+@pytest.mark.parametrize("ml", [0, 1, 4])
+@pytest.mark.parametrize("ms", [40, 300])
+def test_factor_form_equals_literal_formulas_at_the_pcg_shift(ms, ml):
+    """The same identity at the prior shift of the flagship configurations (n_obs = 100000,
+    sigma = 0.5 / 1e6: d = 1 / (n sigma) = 20), where the variance follows a PCG run
+    (test_pcg_paths.py holds the GPU to 1e-8 there): the two references agree to 1e-12."""
+    rng = np.random.default_rng(100 + 10 * ms + ml)
+    n_ref, n_obs, sigma, nt = 300, 100000, 0.5 / 1e6, 17
+    assert 1.0 / (n_obs * sigma) == pytest.approx(20.0, rel=1e-15)
+    Xs = rng.standard_normal((n_ref, ms))
+    Xl = rng.standard_normal((n_ref, ml)) if ml else None
+    Ts = rng.standard_normal((nt, ms))
+    Tl = rng.standard_normal((nt, ml)) if ml else None
+    ss, sl, ll = R.block_sigmas(Xs, Xl, n_ref)
+    lit = R.nt_diag_ls(ll, sl, ss, sigma, n_obs, Tl, Ts) if ml else R.nt_diag_s(ss, sigma, n_obs, Ts)
+    got = factor_form(Xs, Xl, n_ref, n_obs, sigma, Ts, Tl)
+    assert np.max(np.abs(got - lit)) / np.max(np.abs(lit)) < 1e-12
+
+
 # ----------------------------------------------------------------------------- test_dat
 def td_indicator(n_total):
     """No indicator file ships with the reference: every 5th test individual (from the 3rd) is
