@@ -8,6 +8,8 @@ entry points mirror the reference operator interface (fboehm/DBSLMM, scr/dbslmmf
 * ``Plan``                -- the same problem kept resident in HBM for repeated solves.
 * ``bed_maf``             -- the MAF pass of IO::readBim (dtpr.cpp:93-102).
 * ``read_snp_std``        -- IO::readSNPIm + SNPPROC::nomalizeVec for a list of rows.
+* ``Plan.score``          -- the polygenic scores of a target panel for every h2f copy of the latest
+  run (what the reference leaves to ``plink --score``), ``tune_r2`` the R2 index of TUNE.R on them.
 * ``Context.row_stats``   -- the exact per-row integers (sum, sum of squares, missing calls) the
   resident panel image keeps and every per-row statistic derives from (tests, diagnostics).
 
@@ -24,7 +26,7 @@ from . import _lib
 from ._lib import (WORKLOAD_LEN, BLOCK_EMPTY, BLOCK_MONOMORPHIC, BLOCK_NOT_CONVERGED, BLOCK_NOT_PD,
                    BLOCK_OK, KERNEL_NAMES, SOLVER_AUTO, SOLVER_FACTOR, SOLVER_PCG, DbslmmError)
 
-__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks",
+__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2",
            "DbslmmError", "BLOCK_OK", "BLOCK_EMPTY", "BLOCK_NOT_PD", "BLOCK_MONOMORPHIC",
            "BLOCK_NOT_CONVERGED", "KERNEL_NAMES", "SOLVER_AUTO", "SOLVER_FACTOR", "SOLVER_PCG"]
 
@@ -184,6 +186,7 @@ class Plan:
 
     def run(self):
         self.ctx.check(self.ctx.lib.dbslmm_plan_run(self.h), "plan_run")
+        self._run_copies = 1
 
     def sync(self):
         self.ctx.check(self.ctx.lib.dbslmm_plan_sync(self.h), "plan_sync")
@@ -210,6 +213,7 @@ class Plan:
             st = np.zeros((n, p.num_block), dtype=np.int32)
         self.ctx.check(self.ctx.lib.dbslmm_plan_run_multi(self.h, _ptr(sig), n, _ptr(bs), _ptr(bl),
                                                           _ptr(st)), "plan_run_multi")
+        self._run_copies = n
         return [(bs[i], bl[i], st[i]) for i in range(n)]
 
     def enable_timing(self, on: bool = True):
@@ -282,6 +286,57 @@ class Plan:
         self.ctx.check(self.ctx.lib.dbslmm_plan_variance(self.h, C.byref(tp), _ptr(out), _ptr(nt)),
                        "plan_variance")
         return out.reshape(self.prob.num_block, n_test).T
+
+    def score(self, test_bed: np.ndarray, indicator, s_pos, l_pos=None, *, mode="counts", w_s=None, w_l=None,
+              flip_s=None, flip_l=None, chunk_slots=0, n_total=None, n_copies=None):
+        """Polygenic scores of a target panel from the betas of the latest run (dbslmm_plan_score),
+        one row per copy of that run (1 after run(), len(sigmas) after run_multi()): returns
+        (scores[n_copies, n_test], dropped[n_copies]).  indicator: nonzero = selected, or None for
+        every individual of the panel (then n_total = the individuals in its .fam is required);
+        s_pos / l_pos as in variance().  mode "counts": sum beta w g (with w = 1/sqrt(2 maf (1 - maf))
+        the `plink --score 1 2 4 sum` of the effect file); "std": sum beta w (g - mu) / sd over the
+        selected individuals.  flip_*: nonzero = the panel's A1 is the other allele.  dropped[c] =
+        SNPs that contribute nothing to copy c (NaN betas, no observed call, zero variance in "std").
+        The event time of the scoring kernels is kept in self.score_gpu_ms."""
+        p = self.prob
+        modes = {"counts": _lib.SCORE_COUNTS, "std": _lib.SCORE_STD}
+        if mode not in modes:
+            raise ValueError('mode: "counts" or "std"')
+        tb = np.ascontiguousarray(test_bed, dtype=np.uint8)
+        ind = None if indicator is None else np.ascontiguousarray(indicator, dtype=np.int32)
+        if ind is None and n_total is None:
+            raise ValueError("indicator None (all individuals) needs n_total")
+        if ind is not None and n_total is not None and int(n_total) != ind.size:
+            raise ValueError("n_total differs from len(indicator)")
+        nt_all = ind.size if ind is not None else int(n_total)
+        sp = np.ascontiguousarray(s_pos, dtype=np.int32)
+        lp = None if l_pos is None else np.ascontiguousarray(l_pos, dtype=np.int32)
+        if sp.size != p.n_s or (p.n_l and (lp is None or lp.size != p.n_l)):
+            raise ValueError("test s_pos / l_pos must align with the plan's small / large SNPs")
+
+        def per_snp(a, n, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (n,):
+                raise ValueError(f"{what}: one entry per SNP ({n})")
+            return a
+        ws, wl = per_snp(w_s, p.n_s, np.float64, "w_s"), per_snp(w_l, p.n_l, np.float64, "w_l")
+        fs, fl = per_snp(flip_s, p.n_s, np.uint8, "flip_s"), per_snp(flip_l, p.n_l, np.uint8, "flip_l")
+        if n_copies is None:                       # the copies of the latest run (anything else is refused)
+            n_copies = getattr(self, "_run_copies", 0)
+        n_copies = int(n_copies)
+        n_test = nt_all if ind is None else int((ind != 0).sum())
+        scores = np.zeros((max(1, n_copies), n_test))
+        dropped = np.zeros(max(1, n_copies), dtype=np.int32)
+        nt = np.zeros(1, dtype=np.int32)
+        ms = np.zeros(1)
+        args = _lib.ScoreArgs(modes[mode], int(chunk_slots), _ptr(ws), _ptr(wl), _ptr(fs), _ptr(fl))
+        tp = _lib.TestPanel(_ptr(tb), tb.size, nt_all, _ptr(ind), _ptr(sp), _ptr(lp))
+        self.ctx.check(self.ctx.lib.dbslmm_plan_score(self.h, C.byref(tp), C.byref(args), n_copies, _ptr(scores),
+                                                      _ptr(dropped), _ptr(nt), _ptr(ms)), "plan_score")
+        self.score_gpu_ms = float(ms[0])
+        return scores[:n_copies], dropped[:n_copies]
 
     def close(self):
         if self.h:
@@ -360,3 +415,25 @@ def valid_blocks(ctx: Context, bed: np.ndarray, n_ref: int, ptr, pos, z1, z2):
     ctx.check(ctx.lib.dbslmm_valid_blocks(ctx.h, _ptr(bed), bed.size, n_ref, nb, _ptr(ptr), _ptr(pos),
                                           _ptr(z1), _ptr(z2), _ptr(nume), _ptr(deno)), "valid_blocks")
     return nume, deno
+
+
+def tune_r2(scores, pheno) -> tuple[np.ndarray, int]:
+    """The r2 index of software/TUNE.R on the scores of Plan.score: per copy the squared Pearson
+    correlation of its scores with the phenotype over the individuals whose phenotype is not NaN,
+    and the index of the best copy (the first among equals; a copy without variance has r2 NaN and
+    never wins)."""
+    sc = np.atleast_2d(np.asarray(scores, dtype=np.float64))
+    y = np.asarray(pheno, dtype=np.float64)
+    if sc.shape[1] != y.size:
+        raise ValueError("scores: [n_copies, n_test]; pheno: n_test")
+    ok = ~np.isnan(y)
+    yc = y[ok] - y[ok].mean() if ok.any() else y[ok]
+    r2 = np.full(sc.shape[0], np.nan)
+    for c in range(sc.shape[0]):
+        x = sc[c, ok]
+        xc = x - x.mean() if x.size else x
+        den = float(xc @ xc) * float(yc @ yc)
+        if x.size >= 2 and den > 0.0 and np.isfinite(den):
+            r2[c] = float(xc @ yc) ** 2 / den
+    best = int(np.nanargmax(r2)) if np.any(~np.isnan(r2)) else 0
+    return r2, best

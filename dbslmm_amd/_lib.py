@@ -21,16 +21,17 @@ EXPORTS = (
     "dbslmm_ctx_create_multi", "dbslmm_ctx_num_devices", "dbslmm_plan_shard_info",
     "dbslmm_ctx_cache_bed", "dbslmm_ctx_cache_bed_fd", "dbslmm_plan_block_matrix",
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
-    "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges",
+    "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges", "dbslmm_plan_score",
 )
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
 WORKLOAD_LEN = 22
 BLOCK_OK, BLOCK_EMPTY, BLOCK_NOT_PD, BLOCK_MONOMORPHIC, BLOCK_NOT_CONVERGED = 0, 1, 2, 3, 4
 SOLVER_AUTO, SOLVER_FACTOR, SOLVER_PCG = 0, 1, 2
+SCORE_COUNTS, SCORE_STD = 0, 1
 
 
 class Options(C.Structure):
@@ -60,6 +61,14 @@ class TestPanel(C.Structure):
     _fields_ = [
         ("bed", C.c_void_p), ("bed_len", C.c_int64), ("n_total", C.c_int32),
         ("indicator", C.c_void_p), ("s_pos", C.c_void_p), ("l_pos", C.c_void_p),
+    ]
+
+
+class ScoreArgs(C.Structure):
+    """dbslmm_score_args: mode, chunk_slots (0 = the library's constant), weights and flips."""
+    _fields_ = [
+        ("mode", C.c_int32), ("chunk_slots", C.c_int32), ("w_s", C.c_void_p), ("w_l", C.c_void_p),
+        ("flip_s", C.c_void_p), ("flip_l", C.c_void_p),
     ]
 
 
@@ -107,6 +116,7 @@ def load(path: str | None = None):
     L.dbslmm_read_snp_std.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V, V]
     L.dbslmm_valid_blocks.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V, V, V]
     L.dbslmm_plan_variance.argtypes = [V, P(TestPanel), V, V]
+    L.dbslmm_plan_score.argtypes = [V, P(TestPanel), P(ScoreArgs), C.c_int32, V, V, V, V]
     L.dbslmm_ctx_cache_bed.argtypes = [V, V, C.c_int64]
     L.dbslmm_ctx_cache_bed_fd.argtypes = [V, C.c_int, C.c_int64, V]
     L.dbslmm_shard_plan.argtypes = [C.c_int32, V, C.c_int32, C.c_int32, C.c_int32, V, V]

@@ -14,6 +14,11 @@
 // matrix is written to ./variance.txt (arma_ascii, scr/dbslmmfit.cpp:242), evaluated on the GPU
 // from the solve's factorisation (dbslmm_plan_variance); with -h2f it belongs to the last factor,
 // as the reference's file after the driver's last run.
+// --score PREFIX (needs -dat_str; -test_indicator_file optional) writes the polygenic scores of that
+// panel for every -h2f factor to PREFIX.score.txt (dbslmm_plan_score: what the manual leaves to
+// `plink --score <eff>.txt 1 2 4 sum`, Rmd/Manual.Rmd:176-188) and, with -h2f and phenotypes in
+// the .fam, the R2 of every factor and the best one to PREFIX.hval.r2 / PREFIX.hbest.r2
+// (software/TUNE.R, index r2).
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <sys/time.h>
@@ -59,6 +64,7 @@ struct Param {                     // PARAM, scr/dbslmm.hpp:29-45 (initialised h
     int repeat = 0;                 // --repeat N: N more solves of the resident problem (timing)
     int parse_threads = 8;          // --parse-threads N: host parser threads beside the GPU set-up
     string h2f;                     // "0.8,1,1.2": h2 factors of software/DBSLMM.R tuning
+    string score;                   // --score PREFIX: polygenic scores of the -dat_str panel
 };
 
 // The host rows keep string_views into the mmap'd input files (no per-SNP allocation).
@@ -130,7 +136,11 @@ void print_help() {
               << " -h2f      [list]       h2 factors, e.g. 0.8,1,1.2: one Gram, one solve per factor,\n"
               << "                        <eff>_h2f<f>.txt each (software/DBSLMM.R tuning, extension)\n"
               << " --h2f-merged           -h2f: one factorisation per factor instead of one factor +\n"
-              << "                        Chebyshev iteration for the big blocks (extension)\n";
+              << "                        Chebyshev iteration for the big blocks (extension)\n"
+              << " --score   [prefix]     scores of the -dat_str panel (its -test_indicator_file individuals, or\n"
+              << "                        all) from the fitted effects, one column per -h2f factor, as\n"
+              << "                        `plink --score <eff>.txt 1 2 4 sum`: <prefix>.score.txt; with -h2f and\n"
+              << "                        phenotypes in the .fam also <prefix>.hval.r2 / .hbest.r2 (extension)\n";
 }
 
 // DBSLMM::Assign (scr/dbslmm.cpp:67-172): a flag's value is skipped when it starts with '-'.
@@ -167,6 +177,7 @@ void assign(int argc, char** argv, Param& p) {
         else if (!strcmp(a, "--precise-out")) p.precise = true;
         else if (is("--h2f", "-h2f")) { if ((v = take(i))) p.h2f = v; }
         else if (!strcmp(a, "--h2f-merged")) p.h2f_merged = true;
+        else if (!strcmp(a, "--score")) { if ((v = take(i))) p.score = v; }
         else if (!strcmp(a, "--dry-run")) p.dry_run = true;
         else if (!strcmp(a, "--timing")) p.timing = true;
         else if (!strcmp(a, "--repeat")) { if ((v = take(i))) p.repeat = std::max(0, atoi(v)); }
@@ -331,16 +342,89 @@ void to_csr(const vector<Info>& info, const vector<Summ>& summ, int nb, vector<i
     }
 }
 
-// readTestBim (scr/calc_asymptotic_variance.cpp:142-153): the bp (4th tab field) of each line
-vector<long> read_test_bim(const string& path) {
+// readTestBim (scr/calc_asymptotic_variance.cpp:142-153): the bp (4th tab field) of each line;
+// alleles (optional): the line's A1 / A2 (fields 5, 6), which --score orients the effects by
+vector<long> read_test_bim(const string& path, vector<std::array<string, 2>>* alleles = nullptr) {
     vector<long> out;
     std::ifstream f(path);
     string line;
     while (std::getline(f, line)) {
         auto t = split(line, '\t');
         out.push_back(t.size() > 3 ? atol(t[3].c_str()) : 0);
+        if (alleles) alleles->push_back({t.size() > 4 ? t[4] : string(), t.size() > 5 ? t[5] : string()});
     }
     return out;
+}
+
+// --score: FID, IID and phenotype (column 6; NaN for -9 / NA / absent) of every .fam line
+struct Fam { vector<string> fid, iid; vector<double> pheno; };
+Fam read_fam(const string& path) {
+    Fam out;
+    std::ifstream f(path);
+    string line;
+    while (std::getline(f, line)) {
+        std::istringstream is(line);
+        vector<string> t;
+        for (string w; is >> w;) t.push_back(w);
+        out.fid.push_back(t.size() > 0 ? t[0] : string());
+        out.iid.push_back(t.size() > 1 ? t[1] : string());
+        double y = std::nan("");
+        if (t.size() > 5 && t[5] != "-9" && t[5] != "NA") {
+            char* end = nullptr;
+            const double v = strtod(t[5].c_str(), &end);
+            if (end != t[5].c_str() && *end == 0) y = v;
+        }
+        out.pheno.push_back(y);
+    }
+    return out;
+}
+
+// --score: per SNP of a list the writer's weight 1 / sqrt(2 maf (1 - maf)) (0 for a SNP the writer
+// skips: no finite non-scaled effect) and the orientation of the test panel -- its A1 is the effect
+// allele: as is; its A2: flipped; neither: weight 0, counted in *n_mismatch
+void score_weights(const vector<Info>& info, const vector<Summ>& summ, const vector<int32_t>& tpos,
+                   const vector<std::array<string, 2>>& alleles, vector<double>& w, vector<uint8_t>& flip,
+                   long* n_mismatch) {
+    w.assign(info.size(), 0.0);
+    flip.assign(info.size(), 0);
+    for (size_t i = 0; i < info.size(); ++i) {
+        const Summ& s = summ[info[i].summ];
+        const double wt = 1.0 / std::sqrt(2 * s.maf * (1 - s.maf));
+        const std::array<string, 2>& al = alleles[static_cast<size_t>(tpos[i])];
+        if (s.a1 == al[0]) flip[i] = 0;
+        else if (s.a1 == al[1]) flip[i] = 1;
+        else { ++*n_mismatch; continue; }
+        if (std::isfinite(wt)) w[i] = wt;
+    }
+}
+
+// the h2f factor as the output names carry it
+string h2f_tag(double f) {
+    char hh[32];
+    snprintf(hh, sizeof(hh), "%.15g", f);
+    return hh;
+}
+
+// squared Pearson correlation over the pairs with a phenotype (TUNE.R's r2 index); NaN without
+// variance on either side
+double r2_index(const double* x, const vector<double>& y) {
+    long n = 0;
+    long double mx = 0, my = 0;
+    for (size_t i = 0; i < y.size(); ++i)
+        if (!std::isnan(y[i])) { mx += x[i]; my += y[i]; ++n; }
+    if (n < 2) return std::nan("");
+    mx /= n;
+    my /= n;
+    long double sxx = 0, syy = 0, sxy = 0;
+    for (size_t i = 0; i < y.size(); ++i)
+        if (!std::isnan(y[i])) {
+            const long double dx = x[i] - mx, dy = y[i] - my;
+            sxx += dx * dx;
+            syy += dy * dy;
+            sxy += dx * dy;
+        }
+    const long double den = sxx * syy;
+    return den > 0 ? static_cast<double>(sxy * sxy / den) : std::nan("");
 }
 
 // makePosObjectForTestBim (scr/calc_asymptotic_variance.cpp:160-180): pos = the FIRST test .bim
@@ -582,6 +666,8 @@ int main(int argc, char** argv) {
     if (p.t > 100 || p.t < 1) return fail("-t is not correct (1, 100)!");
     if (p.eff.empty()) return fail("-eff is no parameter!");
     if (p.nsnp <= 0 || p.n <= 0) return fail("-n and -nsnp must be positive!");
+    if (!p.score.empty() && p.dat_str.empty())
+        return fail("--score needs -dat_str (the bfile of the panel to score)");
     const bool has_lfile = static_cast<bool>(lf);
     sf.close();
     lf.close();
@@ -718,19 +804,39 @@ int main(int argc, char** argv) {
     }
     // test panel of the variance output (scr/dbslmm.cpp:264-320)
     const bool want_var = !p.dat_str.empty() && !p.test_indicator_file.empty();
-    if (!want_var && (!p.dat_str.empty() || !p.test_indicator_file.empty()))
+    const bool want_score = !p.score.empty();
+    if (!want_var && !want_score && (!p.dat_str.empty() || !p.test_indicator_file.empty()))
         std::cout << "[NOTE] variance.txt needs both -dat_str and -test_indicator_file; skipped.\n";
     vector<int32_t> ts_pos, tl_pos, indicator;
-    if (want_var) {
-        const vector<long> base = read_test_bim(p.dat_str + ".bim");
+    vector<std::array<string, 2>> t_alleles;
+    if (want_var || want_score) {
+        const vector<long> base = read_test_bim(p.dat_str + ".bim", want_score ? &t_alleles : nullptr);
         string err;
         if (!align_test_pos(info_s, add_block(make_pos_for_test_bim(base, inter_s), blocks), summ_s,
                             static_cast<int>(blocks.size()), ts_pos, err) ||
             (has_l && !align_test_pos(info_l, add_block(make_pos_for_test_bim(base, inter_l), blocks), summ_l,
                                       static_cast<int>(blocks.size()), tl_pos, err)))
             return fail("test panel " + p.dat_str + ": " + err);
-        indicator = read_indicator(p.test_indicator_file);
-        if (indicator.empty()) return fail(p.test_indicator_file + " is empty or missing");
+        if (!p.test_indicator_file.empty()) {
+            indicator = read_indicator(p.test_indicator_file);
+            if (indicator.empty()) return fail(p.test_indicator_file + " is empty or missing");
+        }
+    }
+    // --score: the panel's individuals, and per SNP the writer's weight and the panel's orientation
+    Fam fam;
+    vector<double> w_s, w_l;
+    vector<uint8_t> flip_s, flip_l;
+    if (want_score) {
+        fam = read_fam(p.dat_str + ".fam");
+        if (fam.fid.empty()) return fail(p.dat_str + ".fam is empty or missing");
+        if (!indicator.empty() && indicator.size() != fam.fid.size())
+            return fail("-test_indicator_file has " + std::to_string(indicator.size()) + " lines, " + p.dat_str +
+                        ".fam " + std::to_string(fam.fid.size()));
+        long mism = 0;
+        score_weights(info_s, summ_s, ts_pos, t_alleles, w_s, flip_s, &mism);
+        if (has_l) score_weights(info_l, summ_l, tl_pos, t_alleles, w_l, flip_l, &mism);
+        std::cout << "Scoring " << p.dat_str << ": " << mism
+                  << " SNPs whose effect allele is neither allele of the test .bim (weight 0).\n";
     }
 
     const int nb = static_cast<int>(blocks.size());
@@ -806,6 +912,93 @@ int main(int argc, char** argv) {
         dbslmm_plan_destroy(plan);
         return fail(string("dbslmm_plan_run_multi: ") + dbslmm_last_error(ctx));
     }
+    if (want_score) {   // before the variance: its re-solve overwrites the device results of copy 0
+        Mapped tbed;
+        if (!tbed.open(p.dat_str + ".bed")) {
+            dbslmm_plan_destroy(plan);
+            return fail(p.dat_str + ".bed cannot be opened");
+        }
+        const int32_t n_total = static_cast<int32_t>(fam.fid.size());
+        int64_t n_sel = n_total;
+        if (!indicator.empty()) {
+            n_sel = 0;
+            for (int32_t v : indicator) n_sel += v != 0;
+        }
+        vector<double> scores(static_cast<size_t>(nf) * std::max<int64_t>(1, n_sel));
+        vector<int32_t> dropped(nf, 0);
+        dbslmm_test_panel tp{tbed.p, static_cast<int64_t>(tbed.n), n_total, indicator.empty() ? nullptr : indicator.data(),
+                             ts_pos.data(), has_l ? tl_pos.data() : nullptr};
+        dbslmm_score_args sa{};
+        sa.mode = DBSLMM_SCORE_COUNTS;
+        sa.w_s = w_s.data();
+        sa.flip_s = flip_s.data();
+        if (has_l) {
+            sa.w_l = w_l.data();
+            sa.flip_l = flip_l.data();
+        }
+        int32_t n_test = 0;
+        double score_ms = 0.0;
+        rc = dbslmm_plan_score(plan, &tp, &sa, nf, scores.data(), dropped.data(), &n_test, &score_ms);
+        if (rc != DBSLMM_OK) {
+            dbslmm_plan_destroy(plan);
+            return fail(string("dbslmm_plan_score: ") + dbslmm_last_error(ctx));
+        }
+        for (int f = 0; f < nf; ++f)
+            if (dropped[f])
+                std::cout << "Scoring: " << dropped[f] << " SNPs without a usable effect or call contribute nothing"
+                          << (p.h2f.empty() ? string() : " (h2f " + h2f_tag(factors[f]) + ")") << ".\n";
+        string o = "FID IID";
+        for (int f = 0; f < nf; ++f) o += p.h2f.empty() ? string(" SCORE") : " SCORE_h2f" + h2f_tag(factors[f]);
+        o += '\n';
+        vector<double> pheno;                       // of the selected individuals
+        char num[64];
+        int64_t t = 0;
+        for (int32_t i = 0; i < n_total; ++i) {
+            if (!indicator.empty() && indicator[i] == 0) continue;
+            o += fam.fid[i] + ' ' + fam.iid[i];
+            for (int f = 0; f < nf; ++f) {
+                o += ' ';
+                o.append(num, std::to_chars(num, num + sizeof(num), scores[static_cast<size_t>(f) * n_test + t],
+                                            std::chars_format::general, p.precise ? 17 : 6).ptr);
+            }
+            o += '\n';
+            pheno.push_back(fam.pheno[i]);
+            ++t;
+        }
+        {
+            std::ofstream f(p.score + ".score.txt", std::ios::binary);
+            f.write(o.data(), static_cast<std::streamsize>(o.size()));
+            f.close();
+            if (!f) {
+                dbslmm_plan_destroy(plan);
+                return fail(p.score + ".score.txt cannot be written");
+            }
+        }
+        // h2f tuning by the r2 index of software/TUNE.R: R2 of every factor's score, and the best one
+        long n_ph = 0;
+        for (double y : pheno) n_ph += !std::isnan(y);
+        if (!p.h2f.empty() && n_ph >= 2) {
+            std::ofstream hv(p.score + ".hval.r2"), hb(p.score + ".hbest.r2");
+            hv.precision(p.precise ? 17 : 6);
+            int best = -1;
+            double best_r2 = -1.0;
+            for (int f = 0; f < nf; ++f) {
+                const double r2 = r2_index(scores.data() + static_cast<size_t>(f) * n_test, pheno);
+                std::cout << "h2f " << h2f_tag(factors[f]) << ": R2 = " << r2 << "\n";
+                hv << h2f_tag(factors[f]) << ' ' << r2 << '\n';
+                if (!std::isnan(r2) && r2 > best_r2) { best_r2 = r2; best = f; }
+            }
+            if (best < 0) best = 0;
+            hb << h2f_tag(factors[best]) << '\n';
+            std::cout << "Using r2 the best h2 factor: " << h2f_tag(factors[best]) << ".\n";
+            if (!hv || !hb) {
+                dbslmm_plan_destroy(plan);
+                return fail(p.score + ".hval.r2 / .hbest.r2 cannot be written");
+            }
+        }
+        if (p.timing) ph.put("score_gpu_ms", score_ms);
+    }
+    ph.mark("score");
     if (want_var) {
         Mapped tbed;
         if (!tbed.open(p.dat_str + ".bed")) {
@@ -844,8 +1037,7 @@ int main(int argc, char** argv) {
         // output name: <eff>.txt, or with -h2f the driver's <prefix>_h2f<hh>.dbslmm.txt
         string name = p.eff;
         if (!p.h2f.empty()) {
-            char hh[32];
-            snprintf(hh, sizeof(hh), "%.15g", factors[f]);
+            const string hh = h2f_tag(factors[f]);
             const string ext = ".dbslmm";
             if (name.size() > ext.size() && name.compare(name.size() - ext.size(), ext.size(), ext) == 0)
                 name = name.substr(0, name.size() - ext.size()) + "_h2f" + hh + ext;

@@ -668,6 +668,7 @@ static int mp_run(dbslmm_plan* p, const double* sigmas, int n, bool wait) {
         p->stopped = false;
         p->var_copy = n - 1;
         p->sigma_run = sigmas[n - 1];
+        p->score_copies = n;
     }
     return rc;
 }
@@ -735,6 +736,68 @@ static int mp_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* diag
                         n_test * sizeof(double));
         return DBSLMM_OK;
     });
+}
+
+// Scores of every copy of the last run: each job scores what it solved (its subset of the positions,
+// weights and flips; its local copy k is the caller's copy run_copies[k]) and the host adds the
+// jobs' slices in job order.  A units plan returns its own units' contribution.
+static int mp_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_score_args* args, int32_t n_copies,
+                    double* scores, int32_t* dropped, int32_t* n_test_out, double* gpu_ms) {
+    dbslmm_ctx* ctx = p->ctx;
+    int32_t n_test = tp->n_total;
+    if (tp->indicator) {
+        n_test = 0;
+        for (int32_t i = 0; i < tp->n_total; ++i) n_test += tp->indicator[i] != 0;
+    }
+    if (n_test_out) *n_test_out = n_test;
+    if (gpu_ms) *gpu_ms = 0.0;
+    if (dropped) std::fill(dropped, dropped + n_copies, 0);
+    if (n_test == 0) return DBSLMM_OK;
+    ARG_CHECK(ctx, scores, "null scores");
+    std::fill(scores, scores + static_cast<size_t>(n_copies) * n_test, 0.0);
+    auto& S = p->mp->shards;
+    std::vector<std::vector<double>> sc(S.size());
+    std::vector<std::vector<int32_t>> dr(S.size());
+    std::vector<double> ms(S.size(), 0.0);
+    const int rc = fan_out(p, [&](int d) -> int {
+        DeviceShard& sh = S[d];
+        const int nr = static_cast<int>(sh.run_copies.size());
+        if (nr == 0) return DBSLMM_OK;
+        std::vector<int32_t> sp(sh.s_idx.size()), lp(sh.l_idx.size());
+        for (size_t i = 0; i < sp.size(); ++i) sp[i] = tp->s_pos[sh.s_idx[i]];
+        for (size_t i = 0; i < lp.size(); ++i) lp[i] = tp->l_pos[sh.l_idx[i]];
+        dbslmm_test_panel t = *tp;
+        t.s_pos = sp.data();
+        t.l_pos = p->n_l ? lp.data() : nullptr;
+        dbslmm_score_args a{};
+        std::vector<double> ws, wl;
+        std::vector<uint8_t> fs, fl;
+        if (args) {
+            a = *args;
+            if (args->w_s) { ws.resize(sp.size()); for (size_t i = 0; i < sp.size(); ++i) ws[i] = args->w_s[sh.s_idx[i]]; a.w_s = ws.data(); }
+            if (args->w_l) { wl.resize(lp.size()); for (size_t i = 0; i < lp.size(); ++i) wl[i] = args->w_l[sh.l_idx[i]]; a.w_l = wl.data(); }
+            if (args->flip_s) { fs.resize(sp.size()); for (size_t i = 0; i < sp.size(); ++i) fs[i] = args->flip_s[sh.s_idx[i]]; a.flip_s = fs.data(); }
+            if (args->flip_l) { fl.resize(lp.size()); for (size_t i = 0; i < lp.size(); ++i) fl[i] = args->flip_l[sh.l_idx[i]]; a.flip_l = fl.data(); }
+        }
+        sc[d].assign(static_cast<size_t>(nr) * n_test, 0.0);
+        dr[d].assign(nr, 0);
+        return dbslmm_plan_score(sh.plan, &t, &a, nr, sc[d].data(), dr[d].data(), nullptr, &ms[d]);
+    });
+    if (rc != DBSLMM_OK) return rc;
+    for (size_t d = 0; d < S.size(); ++d) {
+        const DeviceShard& sh = S[d];
+        if (sc[d].empty()) continue;
+        for (size_t k = 0; k < sh.run_copies.size(); ++k) {
+            const int c = sh.run_copies[k];
+            if (c >= n_copies) continue;
+            double* o = scores + static_cast<size_t>(c) * n_test;
+            const double* v = sc[d].data() + k * n_test;
+            for (int32_t t = 0; t < n_test; ++t) o[t] += v[t];
+            if (dropped) dropped[c] += dr[d][k];
+        }
+        if (gpu_ms) *gpu_ms = std::max(*gpu_ms, ms[d]);
+    }
+    return DBSLMM_OK;
 }
 
 // MAF pass over contiguous row ranges, one per device.  A range [r0, r1) is handed over as the

@@ -45,6 +45,7 @@
 #include "chol.hip"
 #include "chol_tiled.hip"
 #include "variance.hip"
+#include "score.hip"
 #include "trsv.hip"
 #include "pcg.hip"
 
@@ -212,6 +213,8 @@ struct dbslmm_plan {
     int32_t multi_n = 0;
     hipGraphExec_t graph_multi = nullptr;
     int32_t var_copy = 0;              // copy holding the latest factorisation (variance)
+    int32_t score_copies = 0;          // copies of the latest user run (dbslmm_plan_score)
+    bool score_stale = false;          // the variance's re-solve has overwritten copy 0 of its results
     std::vector<int32_t> h_ld;  // per non-empty block
     std::vector<int32_t> h_m;   // per non-empty block
     std::vector<int32_t> h_tb;  // blocks on the tiled path
@@ -386,6 +389,8 @@ static int mp_run(dbslmm_plan* p, const double* sigmas, int n, bool wait);
 static int mp_sync(dbslmm_plan* p);
 static int mp_block_iters(dbslmm_plan* p, int32_t* iters);
 static int mp_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* diags, int32_t* n_test_out);
+static int mp_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_score_args* args, int32_t n_copies,
+                    double* scores, int32_t* dropped, int32_t* n_test_out, double* gpu_ms);
 static int mp_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int32_t n_ref, int64_t n_snp, double* maf);
 // context-level tools on a multi-device context run on its first device
 #define ON_FIRST_DEVICE(ctx, call)                                       \
@@ -2569,6 +2574,8 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     p->n_runs++;
     p->sigma_run = sigmas[n - 1];
     p->var_copy = n - 1;
+    p->score_copies = n;
+    p->score_stale = false;
     p->pcg_ran = true;
     p->pcg_pending_var = true;
     p->cheb_base = -1;
@@ -2872,6 +2879,12 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     p->n_runs++;
     p->sigma_run = sigmas[n - 1];
     p->var_copy = n - 1;
+    if (p->force_factor) {
+        p->score_stale = true;   // the variance's re-solve: copy 0 of the device results is overwritten
+    } else {
+        p->score_copies = n;
+        p->score_stale = false;
+    }
     {
         p->cheb_base = cheb ? cp.base : -1;
         int iters = 0;
@@ -3342,6 +3355,212 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
     void* bufs[] = {d_tbed, d_cbed, d_tpos, d_sel, d_cpos, d_mu, d_rsd, d_Y, d_diags};
     for (void* q : bufs)
         if (q) (void)hipFree(q);
+    return rc;
+}
+
+// Polygenic scores of the test panel for every copy of the latest run (score.hip).  Two feeders of
+// one kernel: all individuals selected -> the test .bed as a panel image (repitch + row table; the
+// per-slot statistics gathered from the table, rows gathered by the slots' test rows); a subset ->
+// the variance path's compaction + statistics, rows in slot order.
+int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_score_args* args,
+                      int32_t n_copies, double* scores, int32_t* dropped, int32_t* n_test_out,
+                      double* gpu_ms) {
+    if (!p) return DBSLMM_E_ARG;
+    dbslmm_ctx* ctx = p->ctx;
+    if (!p->ran) { ctx->err = "plan_score before plan_run"; return DBSLMM_E_STATE; }
+    if (p->stopped) { ctx->err = "plan_score after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
+    ARG_CHECK(ctx, tp && tp->bed && tp->n_total > 0, "bad test panel");
+    const int32_t mode = args ? args->mode : DBSLMM_SCORE_COUNTS;
+    ARG_CHECK(ctx, mode == DBSLMM_SCORE_COUNTS || mode == DBSLMM_SCORE_STD, "score mode");
+    ARG_CHECK(ctx, !args || args->chunk_slots >= 0, "chunk_slots must be >= 0");
+    ARG_CHECK(ctx, n_copies == p->score_copies, "n_copies must equal the copies of the latest run");
+    ARG_CHECK(ctx, p->n_s == 0 || tp->s_pos, "test panel s_pos missing");
+    ARG_CHECK(ctx, p->n_l == 0 || tp->l_pos, "test panel l_pos missing");
+    if (p->mp) return mp_score(p, tp, args, n_copies, scores, dropped, n_test_out, gpu_ms);
+    if (p->score_stale) {
+        ctx->err = "plan_score after plan_variance re-solved the latest sigma (the device results of copy 0 are "
+                   "overwritten): score before the variance, or run again";
+        return DBSLMM_E_STATE;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (const int rc = pcg_finish(p)) return rc;       // a run still pending
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (const int rc = check_trsv(p)) return rc;
+    std::vector<int32_t> sel;
+    bool all = true;
+    if (tp->indicator) {
+        for (int32_t i = 0; i < tp->n_total; ++i) {
+            if (tp->indicator[i] != 0) sel.push_back(i);
+            else all = false;
+        }
+    }
+    const int32_t n_test = all ? tp->n_total : static_cast<int32_t>(sel.size());
+    if (n_test_out) *n_test_out = n_test;
+    if (gpu_ms) *gpu_ms = 0.0;
+    const int64_t tbps = (tp->n_total + 3) / 4;
+    ARG_CHECK(ctx, tp->bed_len >= 3 + tbps, "test bed image shorter than one SNP row");
+    const int64_t n_rows = (tp->bed_len - 3) / tbps;
+    ARG_CHECK(ctx, n_rows < INT32_MAX, "test bed image has too many rows");
+    std::vector<int32_t> tpos(p->n_slots);
+    for (int32_t s = 0; s < p->n_slots; ++s) {
+        const int32_t o = p->h_slot_out[s];
+        int32_t r = -1;
+        if (o >= 0) r = tp->s_pos[o];
+        else if (o != INT32_MIN) r = tp->l_pos[-1 - o];
+        ARG_CHECK(ctx, o == INT32_MIN || (r >= 0 && r < n_rows), "test SNP bed row out of range");
+        tpos[s] = r;
+    }
+    if (n_test == 0) {
+        if (dropped) std::fill(dropped, dropped + n_copies, 0);
+        return DBSLMM_OK;
+    }
+    ARG_CHECK(ctx, scores, "null scores");
+    const size_t n_out = static_cast<size_t>(n_copies) * n_test;
+    if (p->n_slots == 0 || p->n_nonempty == 0) {       // no SNP: every score is the empty sum
+        std::fill(scores, scores + n_out, 0.0);
+        if (dropped) std::fill(dropped, dropped + n_copies, 0);
+        return DBSLMM_OK;
+    }
+    // (a multiple of the kernel's prefetch depth: a chunk_slots between two multiples acts as the next one)
+    const int32_t chunk_slots = static_cast<int32_t>(std::min<int64_t>(
+        round_up(args && args->chunk_slots > 0 ? args->chunk_slots : score::kChunkSlots, score::kDepth), 1 << 30));
+    const int32_t n_chunks = (p->n_slots + chunk_slots - 1) / chunk_slots;
+    const int64_t stride64 = static_cast<int64_t>(n_chunks) * chunk_slots;   // slots incl. the last chunk's tail
+    ARG_CHECK(ctx, stride64 + score::kDepth < INT32_MAX, "chunk_slots too large");
+    const int32_t stride = static_cast<int32_t>(stride64);
+    const int32_t n_words = (n_test + 15) / 16;
+    const int64_t n_pad = 16 * static_cast<int64_t>(n_words);
+    ARG_CHECK(ctx, n_chunks <= 65535, "chunk_slots too small for this plan (more than 65535 chunks)");
+    const int64_t cpitch = round_up(n_test, 256) / 4;   // the compacted rows in the panel image's format
+    std::vector<int32_t> cpos(p->n_slots);
+    for (int32_t s = 0; s < p->n_slots; ++s) cpos[s] = tpos[s] >= 0 ? s : -1;
+    // the row the product kernel loads for every slot it may touch (a chunk's tail and the
+    // prefetch past it included): a padding slot and the tail read a valid row with a = 0 --
+    // image feeder: the image's zero-dosage row; compaction feeder: the slot's own row (all 11), row 0
+    std::vector<int32_t> srow(static_cast<size_t>(stride) + score::kDepth);
+    for (size_t s = 0; s < srow.size(); ++s) {
+        const bool real = s < static_cast<size_t>(p->n_slots);
+        if (all) srow[s] = real && tpos[s] >= 0 ? tpos[s] : static_cast<int32_t>(n_rows);
+        else srow[s] = real ? static_cast<int32_t>(s) : 0;
+    }
+    std::vector<double> hw_s, hw_l;
+    std::vector<uint8_t> hf_s, hf_l;
+    if (args && args->w_s) hw_s.assign(args->w_s, args->w_s + p->n_s);
+    if (args && args->w_l) hw_l.assign(args->w_l, args->w_l + p->n_l);
+    if (args && args->flip_s) hf_s.assign(args->flip_s, args->flip_s + p->n_s);
+    if (args && args->flip_l) hf_l.assign(args->flip_l, args->flip_l + p->n_l);
+    hipStream_t st = ctx->stream;
+    uint8_t *d_tbed = nullptr, *d_cbed = nullptr, *d_fs = nullptr, *d_fl = nullptr;
+    int32_t *d_tpos = nullptr, *d_sel = nullptr, *d_cpos = nullptr, *d_drop = nullptr, *d_srow = nullptr;
+    double *d_mu = nullptr, *d_rsd = nullptr, *d_ws = nullptr, *d_wl = nullptr, *d_coef = nullptr, *d_kc = nullptr,
+           *d_part = nullptr, *d_scores = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    PanelImage im;
+    const size_t nsl = static_cast<size_t>(p->n_slots);
+    const size_t ncoef = static_cast<size_t>(n_copies) * stride;
+    const int pass_max = std::min<int>(score::kMaxPass, n_copies);
+    int rc = DBSLMM_OK;
+    // synchronous allocations: ordered against other host threads' graph captures
+    std::lock_guard<std::mutex> lk(g_capture_mu);
+    do {
+        hipError_t e;
+        if ((e = hipMalloc(&d_tbed, tp->bed_len + kBedPad)) != hipSuccess ||
+            (e = hipMemsetAsync(d_tbed, 0, tp->bed_len + kBedPad, st)) != hipSuccess ||
+            (e = upload_staged(d_tbed, tp->bed, tp->bed_len, st)) != hipSuccess ||
+            (e = dev_upload(&d_tpos, tpos, st)) != hipSuccess || (e = dev_upload(&d_srow, srow, st)) != hipSuccess ||
+            (e = hipMalloc(&d_mu, nsl * sizeof(double))) != hipSuccess ||
+            (e = hipMalloc(&d_rsd, nsl * sizeof(double))) != hipSuccess ||
+            (e = hipMalloc(&d_coef, 3 * ncoef * sizeof(double))) != hipSuccess ||
+            (e = hipMalloc(&d_kc, static_cast<size_t>(n_copies) * (1 + n_chunks) * sizeof(double))) != hipSuccess ||   // K_c | per chunk
+            (e = hipMalloc(&d_drop, n_copies * sizeof(int32_t))) != hipSuccess ||
+            (e = hipMemsetAsync(d_drop, 0, n_copies * sizeof(int32_t), st)) != hipSuccess ||
+            (e = hipMalloc(&d_part, static_cast<size_t>(n_chunks) * pass_max * n_pad * sizeof(double))) != hipSuccess ||
+            (e = hipMalloc(&d_scores, n_out * sizeof(double))) != hipSuccess ||
+            (!hw_s.empty() && (e = dev_upload(&d_ws, hw_s, st)) != hipSuccess) ||
+            (!hw_l.empty() && (e = dev_upload(&d_wl, hw_l, st)) != hipSuccess) ||
+            (!hf_s.empty() && (e = dev_upload(&d_fs, hf_s, st)) != hipSuccess) ||
+            (!hf_l.empty() && (e = dev_upload(&d_fl, hf_l, st)) != hipSuccess) ||
+            (e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) {
+            ctx->err = std::string("score alloc/upload: ") + hipGetErrorString(e);
+            rc = DBSLMM_E_HIP;
+            break;
+        }
+        const uint8_t* rows = nullptr;    // the 2-bit rows the product reads and their pitch
+        int64_t pitch = 0;
+        if (all) {
+            if ((e = image_from_verbatim(ctx, d_tbed, tp->bed_len, tp->n_total, &im)) != hipSuccess) {
+                ctx->err = std::string("score panel image: ") + hipGetErrorString(e);
+                rc = DBSLMM_E_HIP;
+                break;
+            }
+            hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, st, im.rows(),
+                               tp->n_total, d_tpos, nullptr, p->n_slots, nullptr, d_mu, d_rsd, nullptr);
+            rows = im.mem.get();
+            pitch = im.pitch;
+        } else {
+            if ((e = dev_upload(&d_sel, sel, st)) != hipSuccess || (e = dev_upload(&d_cpos, cpos, st)) != hipSuccess ||
+                (e = hipMalloc(&d_cbed, nsl * cpitch)) != hipSuccess) {   // (dbslmm_test_compact writes every byte)
+                ctx->err = std::string("score alloc/upload: ") + hipGetErrorString(e);
+                rc = DBSLMM_E_HIP;
+                break;
+            }
+            for (int32_t q0 = 0; q0 < p->n_slots; q0 += 32768) {   // (one grid row per slot)
+                const int32_t nq = std::min<int32_t>(32768, p->n_slots - q0);
+                hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cpitch + 255) / 256), nq),
+                                   dim3(256), 0, st, d_tbed, tbps, d_tpos + q0, nq, d_sel, n_test, cpitch,
+                                   d_cbed + static_cast<int64_t>(q0) * cpitch);
+            }
+            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
+                               st, d_cbed, n_test, cpitch, d_cpos, p->n_slots, d_mu, d_rsd);
+            rows = d_cbed;
+            pitch = cpitch;
+        }
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev0, st)) != hipSuccess) {
+            ctx->err = std::string("score statistics: ") + hipGetErrorString(e);
+            rc = DBSLMM_E_HIP;
+            break;
+        }
+        double *d_a = d_coef, *d_am = d_coef + ncoef, *d_k = d_coef + 2 * ncoef;
+        hipLaunchKernelGGL(dbslmm_score_coef, dim3((stride + 255) / 256, n_copies), dim3(256), 0, st,
+                           p->d_slot_out, p->d_slot_block, p->d_blk_id, p->d_status, p->nbk, p->d_beta_s,
+                           p->d_beta_l, p->n_s, p->n_l, d_ws, d_wl, d_fs, d_fl, d_mu, d_rsd, p->n_slots, stride,
+                           n_copies, mode, n_test, d_a, d_am, d_k, d_drop);
+        hipLaunchKernelGGL(dbslmm_score_const, dim3(n_chunks, n_copies), dim3(256), 0, st, d_k, stride, chunk_slots,
+                           static_cast<int64_t>(stride), d_kc + n_copies);
+        hipLaunchKernelGGL(dbslmm_score_const, dim3(1, n_copies), dim3(256), 0, st, d_kc + n_copies, n_chunks, n_chunks,
+                           static_cast<int64_t>(n_chunks), d_kc);
+        const dim3 pgrid((n_words + 255) / 256, n_chunks);
+        for (int c0 = 0; c0 < n_copies; c0 += score::kMaxPass) {   // at most kMaxPass copies per pass
+            const int nc = std::min<int>(score::kMaxPass, n_copies - c0);
+            const double* pa = d_a + static_cast<size_t>(c0) * stride;
+            const double* pam = d_am + static_cast<size_t>(c0) * stride;
+#define DBSLMM_SCORE_PASS(NC)                                                                                   \
+    hipLaunchKernelGGL(dbslmm_score_partial<NC>, pgrid, dim3(256), 0, st, rows, pitch, d_srow, pa, pam, stride, \
+                       chunk_slots, n_words, d_part)
+            if (nc == 1) DBSLMM_SCORE_PASS(1);
+            else if (nc == 2) DBSLMM_SCORE_PASS(2);
+            else if (nc == 3) DBSLMM_SCORE_PASS(3);
+            else DBSLMM_SCORE_PASS(4);
+#undef DBSLMM_SCORE_PASS
+            hipLaunchKernelGGL(dbslmm_score_reduce, dim3((n_test + 255) / 256, nc), dim3(256), 0, st, d_part, n_chunks,
+                               nc, n_pad, d_kc + c0, n_test, d_scores + static_cast<size_t>(c0) * n_test);
+        }
+        float ms = 0.0f;
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev1, st)) != hipSuccess ||
+            (e = hipMemcpyAsync(scores, d_scores, n_out * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (dropped && (e = hipMemcpyAsync(dropped, d_drop, n_copies * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) ||
+            (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) {
+            ctx->err = std::string("score run: ") + hipGetErrorString(e);
+            rc = DBSLMM_E_HIP;
+            break;
+        }
+        if (gpu_ms) *gpu_ms = ms;
+    } while (0);
+    void* bufs[] = {d_tbed, d_cbed, d_fs, d_fl, d_tpos, d_sel, d_cpos, d_drop, d_srow, d_mu, d_rsd, d_ws, d_wl, d_coef, d_kc, d_part, d_scores};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
     return rc;
 }
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 17
+#define DBSLMM_ABI_VERSION 18
 
 enum {
     DBSLMM_OK = 0,
@@ -412,6 +412,51 @@ typedef struct dbslmm_test_panel {
  * n_test_out (optional) receives n_test. */
 int dbslmm_plan_variance(dbslmm_plan* plan, const dbslmm_test_panel* test, double* diags,
                          int32_t* n_test_out);
+
+/* Polygenic scores of a target panel from the betas of the latest run (ABI 18): what the reference
+ * leaves to `plink --score <eff>.txt 1 2 4 sum` (Rmd/Manual.Rmd:176-188), once per h2f factor
+ * (software/DBSLMM.R:204-219, software/TUNE.R), computed on the device for every copy of the run in
+ * one pass over the 2-bit panel (score.hip).
+ *
+ * The panel is a dbslmm_test_panel; indicator == NULL selects all n_total individuals.  Per SNP j
+ * of the plan, over the selected individuals: dosage 00 -> 2, 10 -> 1, 11 -> 0, 01 -> missing; mu_j
+ * = mean of the observed dosages; a missing call takes mu_j (readSNPIm, scr/dtpr.cpp:358-360 =
+ * PLINK's mean imputation); sd_j = N-1 standard deviation of the imputed dosages (nomalizeVec).
+ * A flip flag replaces g by 2 - g (a panel whose A1 is the other allele); w defaults to 1.
+ *   DBSLMM_SCORE_COUNTS  score[c][t] = sum_j beta_jc w_j g'_tj          (w_j = 1/sqrt(2 maf (1-maf)):
+ *                        column 4 of the effect file times allele counts, `--score 1 2 4 sum`)
+ *   DBSLMM_SCORE_STD     score[c][t] = sum_j beta_jc w_j (g'_tj - mu'_j) / sd_j  (the predicted value
+ *                        whose variance dbslmm_plan_variance returns)
+ * A SNP contributes 0 to copy c and is counted in dropped[c] when its block's status for that copy
+ * is NOT_PD / MONOMORPHIC, beta_jc w_j is not finite, no selected call is observed, or (STD) sd_j
+ * is 0 or n_test < 2.  NOT_CONVERGED blocks contribute their iterate, as the effect file does.
+ *
+ * chunk_slots  the plan's slots are summed in runs of this many (0 = the library's constant, 512; a
+ *              value between two multiples of 4 acts as the next multiple), the runs then in order: results are bit-identical from run to run and from device to
+ *              device for a given plan and chunk_slots.  A multi-device context adds its shards'
+ *              scores on the host in shard order, so across device counts scores agree to rounding
+ *              (2 (M + 64) 2^-53 sum_j |a_j| (|g_tj| + |mu_j|), M SNPs), not bit for bit; a units
+ *              plan returns its own units' contribution (zeros elsewhere): the caller adds the ranks.
+ */
+enum { DBSLMM_SCORE_COUNTS = 0, DBSLMM_SCORE_STD = 1 };
+typedef struct dbslmm_score_args {
+    int32_t mode;            /* DBSLMM_SCORE_COUNTS / DBSLMM_SCORE_STD */
+    int32_t chunk_slots;     /* 0 = the library's constant; tests and A/B runs set it */
+    const double* w_s;       /* per small SNP, NULL = 1 */
+    const double* w_l;       /* per large SNP, NULL = 1 */
+    const uint8_t* flip_s;   /* per small SNP, NULL = none */
+    const uint8_t* flip_l;   /* per large SNP, NULL = none */
+} dbslmm_score_args;
+/* args NULL: counts, defaults.  n_copies must equal the copies of the latest run (1 after plan_run,
+ * n_sigma after plan_run_multi); scores = n_copies slices of n_test (n_test_out, the selected
+ * individuals in .fam order); dropped (optional) n_copies entries; gpu_ms (optional) = the event
+ * time of the scoring kernels (a multi-device context: its slowest shard).  Finishes a pending run
+ * first; reads the device betas and statuses and changes neither.  DBSLMM_E_STATE before any run,
+ * after a debug_stop run, and after dbslmm_plan_variance had to re-solve the latest sigma (its
+ * re-solve overwrites the device results of copy 0): score before the variance, or run again. */
+int dbslmm_plan_score(dbslmm_plan* plan, const dbslmm_test_panel* test, const dbslmm_score_args* args,
+                      int32_t n_copies, double* scores, int32_t* dropped, int32_t* n_test_out,
+                      double* gpu_ms);
 
 /* MAF pass: maf[r] for every bed row r < n_snp (readSNPIm with an all-ones indicator). */
 int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
