@@ -80,13 +80,16 @@ def _block_ref(prob, b, sig, thr, pcg=True):
     return out
 
 
-def _diagnose(prob, b, sg, thr, devices=0):
+def _diagnose(prob, b, sg, thr, devices=0, factor=None):
     """Per-phase differences of block b (a full-size mismatch must name its phase):
     Sigma after the Gram (a debug_stop = 1 run, dbslmm_plan_block_matrix) against the oracle's
     standardised Gram, then -- from a fresh full run -- the factor L (strict lower triangle and the
     stored 1 / L_ii), y = L^-1 z (row m) and beta, each against NumPy's Cholesky of the reference
     matrix (scr/dbslmmfit.cpp:697-729 restated as one joint solve).  Returns a dict
-    of normwise differences (phases of a block below the tiled threshold: Sigma and beta only).
+    of normwise differences (phases of a block below the tiled threshold: Sigma and beta only,
+    unless factor names what the block's kernel leaves in its matrix: "full" = L, 1 / L_ii and the
+    y row, as the tiled layout -- dbslmm_chol_large keeps the same; "no_y" = L and 1 / L_ii only --
+    dbslmm_chol_small keeps y in LDS).
     Runs the factorisation route (solver = 1): its beta is that route's, beside the failing one."""
     from scipy.linalg import solve_triangular
     from dbslmm_amd import Context, Plan
@@ -135,11 +138,14 @@ def _diagnose(prob, b, sg, thr, devices=0):
     del M, S
     y = solve_triangular(L, z, lower=True)
     x = solve_triangular(L.T, y, lower=False) / np.sqrt(prob.n_obs)
-    if m >= 384:     # the tiled layout (default tiled_min at full scale)
+    if factor is None:
+        factor = "full" if m >= 384 else ""     # the tiled layout (default tiled_min at full scale)
+    if factor:
         st = np.tril_indices(m, -1)
         out["L"] = float(np.max(np.abs(A[:m, :m][st] - L[st])) / np.max(np.abs(L)))
         out["L_diag"] = normwise(1.0 / np.diag(A)[:m], np.diag(L))
-        out["y"] = normwise(A[m, :m], y)
+        if factor == "full":
+            out["y"] = normwise(A[m, :m], y)
     out["beta"] = normwise(got, x)
     return out
 

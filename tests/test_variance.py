@@ -228,6 +228,7 @@ def synth_variance_case(seed=3, n_ref=300, n_total=150, mono_block=None):
 
 
 def synth_oracle(prob, tbed, ind, ts_pos, tl_pos, sigma=None):
+    """The literal formulas per block at the problem's tau (0.8 unless the case sets another)."""
     sigma = prob.sigma_s if sigma is None else sigma
     D = np.zeros((int(ind.sum()), prob.num_block))
     for b in range(prob.num_block):
@@ -241,13 +242,13 @@ def synth_oracle(prob, tbed, ind, ts_pos, tl_pos, sigma=None):
             if rl.size:
                 Xl = R.read_block_matrix(prob.bed, rl, prob.n_ref)
                 Tl = R.read_test_block_matrix(tbed, tl_pos[prob.l_ptr[b]:prob.l_ptr[b + 1]], ind)
-                ss, sl, ll = R.block_sigmas(Xs, Xl, prob.n_ref)
+                ss, sl, ll = R.block_sigmas(Xs, Xl, prob.n_ref, prob.tau)
                 try:
                     D[:, b] = R.nt_diag_ls(ll, sl, ss, sigma, prob.n_obs, Tl, Ts)
                 except np.linalg.LinAlgError:
                     D[:, b] = np.nan
             else:
-                ss, _, _ = R.block_sigmas(Xs, None, prob.n_ref)
+                ss, _, _ = R.block_sigmas(Xs, None, prob.n_ref, prob.tau)
                 try:
                     D[:, b] = R.nt_diag_s(ss, sigma, prob.n_obs, Ts)
                 except np.linalg.LinAlgError:
