@@ -861,8 +861,9 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_update(Pc
 // uint16 Gram is solved by ONE workgroup per Krylov sequence (a multi-shift block: one for every
 // copy; a block with large SNPs: one per copy) from the right-hand side to convergence (a persistent grid of one workgroup per CU
 // takes the blocks from a counter, so the chip-wide kernels keep half of every CU): per iteration the block's quadrants are
-// streamed once (the 8 x 8 lane sub-blocks and reduce-scatters of quad_mul16, next quadrant in
-// flight), each wave adding its row and column sums into its own LDS copy of y (fixed order, no
+// streamed once (the 8 x 8 lane sub-blocks and reduce-scatters of quad_mul16, two quadrants in
+// flight -- across the reductions and into the next iteration too), each wave adding its row and
+// column sums into its own LDS copy of y (fixed order, no
 // atomics), then w, the dots, the coefficients, the convergence test and the update exactly as
 // dbslmm_pcg_rows / dbslmm_pcg_update compute them -- with no partial slots, no per-iteration
 // launches and no hand-off between workgroups.  Thread t owns slots t + 256 q (q < kFPer): r, s
@@ -871,9 +872,6 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_update(Pc
 // status at its end (put_beta / put_status, as dbslmm_pcg_final does for the others), so a
 // streamed run's results leave the GPU block by block while the kernel runs.
 // ------------------------------------------------------------------------------------------
-#ifndef PCG_BLOCK_DEPTH
-#define PCG_BLOCK_DEPTH 3   // quadrant buffers per wave in dbslmm_pcg_block (2: one in flight)
-#endif
 namespace pcg {
 // sum of v over the workgroup, every thread gets the total (fixed order: lanes, then waves 0..3)
 template <int N>
@@ -910,11 +908,58 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
     double* red = Pl + n * kFRows;           // block_sum scratch
     if (a.done[bi] != 3) return;             // (monomorphic, or missing calls: the chip-wide path)
     const PcgBlk B = a.blk[bi];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: the quadrant positions stay scalar)
     const int m = B.m, Tb = B.Tb;
     const bool msh = cc < 0;
     const int nx = msh ? n : 1;              // copies of x this sequence yields
     const double dc = msh ? col_shift(a, B, 0) : a.dshift[cc];   // the sequence's shift (the seed's: multi-shift)
+    // quadrants of the block's lower triangle (rows and columns < m), dealt to the waves in turn:
+    // wave w takes positions w, w + 4, .. of the row-major order, nw of them
+    const int Q = (m + 63) / 64;
+    const int nq = Q * (Q + 1) / 2;
+    const int nw = (nq + 3 - wave) >> 2;
+    const int64_t ld16 = static_cast<int64_t>(Tb) * kT;
+    const int rg = lane >> 3, cg = lane & 7;
+    // a position and its quadrant (qi, qj), advanced in row-major lower-triangle order (integers only)
+    struct QPos {
+        int t, qi, qj;
+    };
+    auto adv = [](QPos& p, int k) {
+        p.t += k;
+        p.qj += k;
+        while (p.qj > p.qi) {
+            p.qj -= p.qi + 1;
+            ++p.qi;
+        }
+    };
+    QPos first{0, 0, 0};
+    adv(first, wave);
+    QPos second = first;
+    adv(second, 4);
+    // The block's Gram through a range-checked buffer descriptor: a sub-block row wholly above the
+    // diagonal or past m, and every quadrant past the last (t >= nq), reads at an offset beyond the
+    // range -- zeros with no memory access -- so each load() issues exactly 8 loads unconditionally
+    // and the waits before mult() count only the quadrant they need (with the loads under branches
+    // the compiler waited for all of them, vmcnt(0): one quadrant in flight, 16.5 GB/s per CU).
+    const __amdgpu_buffer_rsrc_t g16 = g16_rsrc(a.G16 + B.off16, static_cast<uint32_t>(ld16 * ld16 * 2));
+    auto load = [&](const QPos& p, pcg_u4 (&raw)[8]) {
+        const int r0 = 64 * p.qi + 8 * rg, c0 = 64 * p.qj + 8 * cg;
+        const bool skip = p.t >= nq || c0 >= m || (p.qi == p.qj && cg > rg);
+        const uint32_t o = static_cast<uint32_t>((r0 * static_cast<int>(ld16) + c0) * 2);
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr)
+            raw[rr] = __builtin_amdgcn_raw_buffer_load_b128(
+                g16, (skip || r0 + rr >= m) ? kG16Oob : o + static_cast<uint32_t>(rr * ld16 * 2), 0, 0);
+    };
+    // Three quadrant buffers per wave, rotated: two in flight while one is multiplied.  G does not
+    // depend on the iterate, so the wave's first two quadrants of an iteration are loaded during
+    // the one before (here: during the set-up) and ra / rb stay live through the reductions, the
+    // coefficients and the update.  The loads issued in the last iteration are in range and
+    // nothing reads them.
+    pcg_u4 ra[8], rb[8], rc[8];
+    load(first, ra);
+    load(second, rb);
     // ---- state: x = p = 0, r = z, s = w = 0, U = rsd o r / diag
     // (S and rsd of the thread's slots in registers: no global reads inside the iterations)
     double r[kFPer], sv[kFPer], wv[kFPer], Sr[kFPer], Rr[kFPer], sg[1] = {0.0};
@@ -937,37 +982,8 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
     }
     block_sum(sg, red, tid);
     double sig = sg[0];
-    // quadrants of the block's lower triangle (rows and columns < m), dealt to the waves in turn
-    const int Q = (m + 63) / 64;
-    const int nq = Q * (Q + 1) / 2;
-    const int64_t ld16 = static_cast<int64_t>(Tb) * kT;
-    const int rg = lane >> 3, cg = lane & 7;
-    auto quad_of = [&](int t, int& qi, int& qj) {   // t-th lower-triangle quadrant, row-major
-        qi = static_cast<int>((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);
-        while (qi * (qi + 1) / 2 > t) --qi;
-        while ((qi + 1) * (qi + 2) / 2 <= t) ++qi;
-        qj = t - qi * (qi + 1) / 2;
-    };
-    // The block's Gram through a range-checked buffer descriptor: a sub-block row wholly above the
-    // diagonal or past m, and every quadrant past the last (t >= nq), reads at an offset beyond the
-    // range -- zeros with no memory access -- so each load() issues exactly 8 loads unconditionally
-    // and the waits before mult() count only the quadrant they need (with the loads under branches
-    // the compiler waited for all of them, vmcnt(0): one quadrant in flight, 16.5 GB/s per CU).
-    const __amdgpu_buffer_rsrc_t g16 = g16_rsrc(a.G16 + B.off16, static_cast<uint32_t>(ld16 * ld16 * 2));
-    auto load = [&](int t, pcg_u4 (&raw)[8]) {
-        int qi, qj;
-        quad_of(t, qi, qj);
-        const int r0 = 64 * qi + 8 * rg, c0 = 64 * qj + 8 * cg;
-        const bool skip = t >= nq || c0 >= m || (qi == qj && cg > rg);
-        const uint32_t o = static_cast<uint32_t>((r0 * static_cast<int>(ld16) + c0) * 2);
-#pragma unroll
-        for (int rr = 0; rr < 8; ++rr)
-            raw[rr] = __builtin_amdgcn_raw_buffer_load_b128(
-                g16, (skip || r0 + rr >= m) ? kG16Oob : o + static_cast<uint32_t>(rr * ld16 * 2), 0, 0);
-    };
-    auto mult = [&](int t, const pcg_u4 (&raw)[8]) {
-        int qi, qj;
-        quad_of(t, qi, qj);
+    auto mult = [&](const QPos& p, const pcg_u4 (&raw)[8]) {
+        const int qi = p.qi, qj = p.qj;
         const bool dq = qi == qj;
         double vi[8], vj[8], racc[8], cacc[8];
 #pragma unroll
@@ -1019,40 +1035,40 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
         // ---- product y = G U (U in LDS since the last update)
         __syncthreads();
         {
-#if PCG_BLOCK_DEPTH == 3
-            // two quadrants in flight while one is multiplied (three register buffers, rotated)
-            // (loads past the last quadrant are out of range: issued, no memory access)
-            pcg_u4 ra[8], rb[8], rc[8];
-            int t = wave;
-            load(t, ra);
-            load(t + 4, rb);
-            while (t < nq) {
-                load(t + 8, rc);
-                mult(t, ra);
-                t += 4;
-                if (t >= nq) break;
-                load(t + 8, ra);
-                mult(t, rb);
-                t += 4;
-                if (t >= nq) break;
-                load(t + 8, rb);
-                mult(t, rc);
-                t += 4;
+            // Steady state: three multiplications in a row, each with the load two positions ahead
+            // issued before it (positions past the wave's last are out of range: issued, no memory
+            // access).  The wave's last one to three are multiplied below, and the first two loads
+            // of the next iteration go out between them.
+            QPos pm = first, pl = second;
+            adv(pl, 4);
+            int s = 0;
+            for (; s + 3 < nw; s += 3) {
+                load(pl, rc);
+                adv(pl, 4);
+                mult(pm, ra);
+                adv(pm, 4);
+                load(pl, ra);
+                adv(pl, 4);
+                mult(pm, rb);
+                adv(pm, 4);
+                load(pl, rb);
+                adv(pl, 4);
+                mult(pm, rc);
+                adv(pm, 4);
             }
-#else
-            pcg_u4 ra[8], rb[8];
-            int t = wave;
-            load(t, ra);
-            while (t < nq) {
-                load(t + 4, rb);
-                mult(t, ra);
-                t += 4;
-                if (t >= nq) break;
-                load(t + 4, ra);
-                mult(t, rb);
-                t += 4;
+            if (nw > 0) {
+                const int rem = nw - s;            // 1, 2 or 3
+                load(pl, rc);                      // (out of range unless rem == 3)
+                mult(pm, ra);
+                adv(pm, 4);
+                load(first, ra);
+                if (rem >= 2) {
+                    mult(pm, rb);
+                    adv(pm, 4);
+                }
+                load(second, rb);
+                if (rem >= 3) mult(pm, rc);
             }
-#endif
         }
         __syncthreads();
         // ---- w = M u, dots r.u, w.u, r.r and x.x per copy (dbslmm_pcg_rows)
@@ -1197,13 +1213,9 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
 }
 
 extern "C" __global__ __launch_bounds__(pcg::kThreads)
-#if PCG_BLOCK_DEPTH == 3
 // one wave per SIMD (its LDS allows one workgroup per CU); at most 312 VGPRs, so a chip-wide
 // product wave (192) still fits beside it on every SIMD
 __attribute__((amdgpu_waves_per_eu(1, 8), amdgpu_num_vgpr(312)))
-#else
-__attribute__((amdgpu_waves_per_eu(2, 8)))
-#endif
 void dbslmm_pcg_block(PcgArgs a, const int2* __restrict__ list, int32_t n_list, int32_t* __restrict__ next,
                       int32_t maxit) {
     // blocks taken in list order (biggest first) by whichever workgroup is free: the next index from
