@@ -256,12 +256,11 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_bed_repitch(
 //   slot_pos       image row of each slot (< 0: padding slot, zeros); null: slot k = row k.
 //   slot_block     flag index of each slot; null: the slot itself (per-row missing indicator).
 // ------------------------------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(256) void dbslmm_slot_stats(
-    const v4i* __restrict__ tab, int32_t n_ref,
+__device__ __forceinline__ void slot_stats_of(
+    int slot, const v4i* __restrict__ tab, int32_t n_ref,
     const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
     double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
     int32_t* __restrict__ block_flags) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= n_slots) return;
     const int32_t pos = slot_pos ? slot_pos[slot] : slot;
     double ds = 0.0, mu = 0.0, rsd = 0.0;       // padding slot
@@ -275,6 +274,43 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_slot_stats(
     if (mu_out) mu_out[slot] = mu;
     if (rsd_out) rsd_out[slot] = rsd;
     if (nmiss > 0 && block_flags) atomicOr(block_flags + (slot_block ? slot_block[slot] : slot), 1);
+}
+
+extern "C" __global__ __launch_bounds__(256) void dbslmm_slot_stats(
+    const v4i* __restrict__ tab, int32_t n_ref,
+    const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
+    double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
+    int32_t* __restrict__ block_flags) {
+    slot_stats_of(blockIdx.x * blockDim.x + threadIdx.x, tab, n_ref, slot_pos, slot_block, n_slots, S_out, mu_out,
+                  rsd_out, block_flags);
+}
+
+// The PCG route's one launch in front of the Gram: dbslmm_slot_stats, and with it what the run
+// resets -- every copy's block status, the count of iterating blocks, dbslmm_pcg_block's sequence
+// counter -- and the copies' prior shifts 1 / (sigma_c n), passed by value.  (block_flags is not
+// reset here: bit 0 is a function of the panel alone, zeroed when the plan is created, and a
+// workgroup that cleared it could not be ordered against another one's atomicOr.)
+constexpr int kFrontCopies = 4;
+struct PcgFront {
+    double shift[kFrontCopies];
+    double* dshift;                 // [n] <- shift
+    int32_t n;
+    int32_t n_status;
+    int32_t* status;                // [n_status] <- 0
+    int32_t* active;                // <- 0
+    int32_t* next;                  // [4] <- 0, or null
+};
+extern "C" __global__ __launch_bounds__(256) void dbslmm_pcg_front(
+    const v4i* __restrict__ tab, int32_t n_ref,
+    const int32_t* __restrict__ slot_pos, const int32_t* __restrict__ slot_block, int32_t n_slots,
+    double* __restrict__ S_out, double* __restrict__ mu_out, double* __restrict__ rsd_out,
+    int32_t* __restrict__ block_flags, PcgFront f) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
+    for (int i = t; i < f.n_status; i += nt) f.status[i] = 0;
+    if (t < f.n) f.dshift[t] = t == 0 ? f.shift[0] : t == 1 ? f.shift[1] : t == 2 ? f.shift[2] : f.shift[3];
+    if (t == 0) *f.active = 0;
+    if (t < 4 && f.next) f.next[t] = 0;
+    slot_stats_of(t, tab, n_ref, slot_pos, slot_block, n_slots, S_out, mu_out, rsd_out, block_flags);
 }
 
 // ------------------------------------------------------------------------------------------

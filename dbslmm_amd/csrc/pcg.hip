@@ -63,6 +63,12 @@ constexpr int kThreads = 256;
 constexpr int kFTb = 8;           // dbslmm_pcg_block: blocks of at most kFTb tile rows (1024 slots)
 constexpr int kFRows = kFTb * kT;
 constexpr int kFPer = kFRows / kThreads;   // rows per thread
+// The chip-wide kernels (product, rows, update) run at the highest wave priority: beside
+// dbslmm_pcg_block they share every SIMD with one of its waves, and the PCG phase ends with them --
+// at equal priority an iteration of theirs took 2.1 x as long beside the block kernel as alone
+// and 0.9 ms of them were left when it ended (config 4); ahead of it, the phase is 0.09 ms
+// shorter there and 0.15 ms at config 5 (profiles/r12).  dbslmm_pcg_block stays at priority 0.
+__device__ __forceinline__ void chip_wide_priority() { __builtin_amdgcn_s_setprio(3); }
 // symv LDS per wave: the staged rsd o u of the item's tile row and of two tile columns, and the
 // reduce-scattered row / column sums ([2][copy][64] each)
 constexpr int wave_lds_doubles(int nc) { return 3 * nc * kVS + 4 * nc * 64; }
@@ -281,6 +287,15 @@ __device__ __forceinline__ double cvt_hi(uint32_t w) {
 
 typedef uint32_t pcg_u4 __attribute__((ext_vector_type(4)));
 
+// The eight elements of one sub-block row (four dwords), converted together ahead of the row's 16
+// FMAs: with each conversion directly in front of its two dependent FMAs the compiler pads most of
+// them with an s_nop (834 in dbslmm_pcg_block, 240 in dbslmm_pcg_symv16; 228 and 62 this way), and
+// the whole-block kernel alone runs 6 % longer (profiles/r12).  Same values, same FMA order.
+__device__ __forceinline__ void cvt_row(const pcg_u4& w, double (&g)[8]) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) g[c] = (c & 1) ? cvt_hi(w[c >> 1]) : cvt_lo(w[c >> 1]);
+}
+
 // A range-checked buffer descriptor over `bytes` of the integer Gram from `base` (wave-uniform: its
 // inputs go through readfirstlane, as 32-bit unsigned halves -- readfirstlane returns int, and a
 // low half >= 2^31 widened as int would set the high word).  A load at an offset >= bytes returns
@@ -314,25 +329,27 @@ __device__ __forceinline__ void quad_mul16(const pcg_u4 (&raw)[8], bool diagq, i
         }
         if (!diagq) {
 #pragma unroll
-            for (int r = 0; r < 8; ++r)
+            for (int r = 0; r < 8; ++r) {
+                double g[8];
+                cvt_row(raw[r], g);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
-                    const uint32_t w = raw[r][c >> 1];
-                    const double g = (c & 1) ? cvt_hi(w) : cvt_lo(w);
-                    racc[r] = __builtin_fma(g, vj[c], racc[r]);
-                    cacc[c] = __builtin_fma(g, vi[r], cacc[c]);
+                    racc[r] = __builtin_fma(g[c], vj[c], racc[r]);
+                    cacc[c] = __builtin_fma(g[c], vi[r], cacc[c]);
                 }
+            }
         } else {
 #pragma unroll
-            for (int r = 0; r < 8; ++r)
+            for (int r = 0; r < 8; ++r) {
+                double g[8];
+                cvt_row(raw[r], g);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
-                    const uint32_t w = raw[r][c >> 1];
-                    const double g = (c & 1) ? cvt_hi(w) : cvt_lo(w);
                     const int dd = 8 * (cg - rg) + c - r;   // j - i
-                    racc[r] = __builtin_fma(dd <= 0 ? g : 0.0, vj[c], racc[r]);
-                    cacc[c] = __builtin_fma(dd < 0 ? g : 0.0, vi[r], cacc[c]);
+                    racc[r] = __builtin_fma(dd <= 0 ? g[c] : 0.0, vj[c], racc[r]);
+                    cacc[c] = __builtin_fma(dd < 0 ? g[c] : 0.0, vi[r], cacc[c]);
                 }
+            }
         }
         rsum[k * 64 + lane] += rscatter8<4, 2, 1>(racc, lane);
         csum[k * 64 + lane] += rscatter8<32, 16, 8>(cacc, lane);
@@ -490,13 +507,19 @@ __device__ void symv_item(const PcgArgs& a, int4 item, int lane, double* vI, dou
 // r = z (every product column), the partial S.(rsd o u) of the first product.  Tile row 0 also
 // resets the block's counters and recurrence state and flags a monomorphic block (a zero-variance
 // SNP: the reference's 0/0 column, beta NaN for the whole block, status MONOMORPHIC) as done.
+// Workgroup g takes rows[g] for g < n_lead and rows[g + skip] past them; an entry with tile row -1
+// is a header: tile row 0's resets and scan alone, for a block dbslmm_pcg_block solves whole (its
+// vectors live in LDS; a monomorphic one is left to dbslmm_pcg_final, which reads no vector).
 // ------------------------------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_init(PcgArgs a, const int2* __restrict__ rows) {
+extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_init(PcgArgs a, const int2* __restrict__ rows,
+                                                                            int32_t n_lead, int32_t skip) {
     using namespace pcg;
     __shared__ double red[kThreads / 64][kMaxNC];
     __shared__ int mono_s;
-    const int2 it = rows[blockIdx.x];
-    const int bi = it.x, I = it.y, tid = threadIdx.x;
+    const int g = blockIdx.x;
+    const int2 it = rows[g < n_lead ? g : g + skip];
+    const bool head = it.y < 0;
+    const int bi = it.x, I = head ? 0 : it.y, tid = threadIdx.x;
     const PcgBlk B = a.blk[bi];
     const bool u16 = on_u16(a, B);
     const int n = a.ncopy, nc = B.nc;
@@ -520,6 +543,7 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_init(PcgA
             if (!mono_s && !fz) atomicAdd(a.active, 1);
         }
     }
+    if (head) return;
     // rows 0..127 of the tile row, two halves of the columns
     const int r = tid & (kT - 1), h = tid >> 7, i = I * kT + r;
     const bool in = i < B.m;
@@ -572,6 +596,7 @@ template <bool U16>
 __device__ __forceinline__ void symv_body(const PcgArgs& a, const int4* __restrict__ items, int32_t n_items) {
     using namespace pcg;
     extern __shared__ double vlds[];
+    chip_wide_priority();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int e = blockIdx.x * kWaves + wave;
     if (e >= n_items) return;
@@ -599,6 +624,7 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_rows(PcgA
     using namespace pcg;
     __shared__ double red[kThreads / 64][kMaxNC][4];
     __shared__ double sig[kMaxNC];
+    chip_wide_priority();
     const int2 it = rows[blockIdx.x];
     const int bi = it.x, I = it.y, tid = threadIdx.x;
     if (a.done[bi]) return;
@@ -684,6 +710,7 @@ extern "C" __global__ __launch_bounds__(pcg::kThreads) void dbslmm_pcg_update(Pc
     __shared__ double seedc[2];          // multi-shift: the seed's alpha, beta
     __shared__ int run_s[kMaxNC];
     __shared__ double red[kThreads / 64][kMaxNC];
+    chip_wide_priority();
     const int2 it = rows[blockIdx.x];
     const int bi = it.x, I = it.y, tid = threadIdx.x;
     if (a.done[bi]) return;
@@ -994,25 +1021,27 @@ __device__ __forceinline__ void pcg_block_solve(const PcgArgs& a, int bi, int cc
         }
         if (!dq) {
 #pragma unroll
-            for (int rr = 0; rr < 8; ++rr)
+            for (int rr = 0; rr < 8; ++rr) {
+                double g[8];
+                cvt_row(raw[rr], g);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
-                    const uint32_t w = raw[rr][c >> 1];
-                    const double g = (c & 1) ? cvt_hi(w) : cvt_lo(w);
-                    racc[rr] = __builtin_fma(g, vj[c], racc[rr]);
-                    cacc[c] = __builtin_fma(g, vi[rr], cacc[c]);
+                    racc[rr] = __builtin_fma(g[c], vj[c], racc[rr]);
+                    cacc[c] = __builtin_fma(g[c], vi[rr], cacc[c]);
                 }
+            }
         } else {
 #pragma unroll
-            for (int rr = 0; rr < 8; ++rr)
+            for (int rr = 0; rr < 8; ++rr) {
+                double g[8];
+                cvt_row(raw[rr], g);
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
-                    const uint32_t w = raw[rr][c >> 1];
-                    const double g = (c & 1) ? cvt_hi(w) : cvt_lo(w);
                     const int dd = 8 * (cg - rg) + c - rr;   // j - i
-                    racc[rr] = __builtin_fma(dd <= 0 ? g : 0.0, vj[c], racc[rr]);
-                    cacc[c] = __builtin_fma(dd < 0 ? g : 0.0, vi[rr], cacc[c]);
+                    racc[rr] = __builtin_fma(dd <= 0 ? g[c] : 0.0, vj[c], racc[rr]);
+                    cacc[c] = __builtin_fma(dd < 0 ? g[c] : 0.0, vi[rr], cacc[c]);
                 }
+            }
         }
         double* y = yw + wave * kFRows;
         const int ri = 64 * qi + 8 * rg + cg, ci = 64 * qj + 8 * cg + rg;

@@ -302,12 +302,14 @@ struct dbslmm_plan {
     int2* d_prow = nullptr;
     int32_t n_pblk = 0, n_pitem = 0, n_prow = 0;
     int32_t n_pitem_chip = 0, n_prow_chip = 0;   // ... of them, those of the chip-wide blocks (listed first)
+    int32_t n_phead = 0;           // d_prow's tail past n_prow: one (block, -1) per block solved whole
     bool pcg_trim = false;         // launch only those: no block dbslmm_pcg_block takes has missing calls
     int32_t pcg_run = pcg::kRunMax;  // tiles per product item (pcg_layout)
     bool pcg_fused = true;         // small one-column blocks solved whole by dbslmm_pcg_block
     int2* d_pflist = nullptr;      // ... their (PcgBlk, copy) sequences (biggest first)
     int32_t* d_pfnext = nullptr;   // ... the next list index to take (16 B, zeroed per run)
     int32_t n_pflist = 0;
+    int32_t pcg_block_wgs = 0;     // dbslmm_options.pcg_block_wgs: a cap on dbslmm_pcg_block's workgroups (0: none)
     std::vector<char> h_pfused;    // per PcgBlk: 1 = in that list
     std::vector<int32_t> h_pnseq;  // ... its sequences there (1, or the copies with large SNPs)
     bool pcg_join = false;         // the main stream still has to wait for dbslmm_pcg_block
@@ -1087,10 +1089,11 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
                    op.sub_grid_lead >= 0 && op.sub_grid_rest >= 0 && op.shard_copies >= 0 &&
                    op.shard_copies <= 64 && op.h2f_iter >= 0 && op.h2f_iter <= 2 && op.solver >= 0 &&
                    op.solver <= 2 && op.pcg_tol >= 0.0 && op.pcg_maxit >= 0 && op.stream_out >= -1 &&
-                   op.stream_out <= 1, "bad dbslmm_options");
+                   op.stream_out <= 1 && op.pcg_block_wgs >= 0, "bad dbslmm_options");
     p->solver = op.solver;
     p->pcg_fused = op.pcg_whole >= 0;
     p->stream_out = op.stream_out >= 0;
+    p->pcg_block_wgs = op.pcg_block_wgs;
     if (op.pcg_tol > 0.0) p->pcg_tol = std::max(1e-15, op.pcg_tol);
     if (op.pcg_maxit > 0) p->pcg_maxit = op.pcg_maxit;
     p->pcg_g16 = 4 * static_cast<int64_t>(pr->n_ref) <= 65535;
@@ -1481,6 +1484,8 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     const size_t nbk = std::max<int32_t>(1, std::max(p->n_nonempty, p->num_block));
     p->nbk = static_cast<int64_t>(nbk);
     if ((e = hipMalloc(&p->d_flags, nbk * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc flags");
+    // (zeroed here for the PCG route, whose front kernel only sets bits: run_pcg)
+    if ((e = hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), ctx->stream)) != hipSuccess) return fail("hipMemset flags");
     // (the block matrices, betas, status and sigma scalars are allocated by the first run, for as
     // many factorisation copies as it solves: ensure_copies -- an h2f plan is not sized twice)
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail("plan set-up");
@@ -1515,14 +1520,21 @@ static int collect_timing(dbslmm_plan* p) {
         // backward of the two groups ends on two streams (8: lead, 11: rest) and the Chebyshev
         // passes start there: tiled = 6 -> max(8, 11), trsv = min(8, 11) -> 7 (the spans overlap)
         float t[kEvPerRun] = {0.f};
+        if (r < static_cast<int>(p->run_route.size()) && p->run_route[r]) {
+            // PCG: statistics, Gram, iterations; the only instants this route records are 0, 1, 2, 3, 4, 7
+            for (int k : {1, 2, 3, 4, 7}) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[0], e[k]));
+            float span[DBSLMM_K_COUNT] = {0.f};
+            span[DBSLMM_K_UNPACK] = t[1];
+            span[DBSLMM_K_GRAM] = t[2] - t[1];
+            span[DBSLMM_K_PCG] = t[7] - t[2];
+            span[DBSLMM_K_PCG_BLOCK] = t[4] - t[3];   // (inside the PCG span, on the second stream)
+            for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
+            p->ms_runs++;
+            continue;
+        }
         for (int k = 1; k < kEvPerRun; ++k) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[0], e[k]));
         const float fend = std::max(t[8], t[11]), cstart = std::min(t[8], t[11]);
         float span[DBSLMM_K_COUNT] = {t[1], t[2] - t[1], t[3] - t[2], t[5] - t[4], fend - t[6], t[7] - cstart, 0.f, 0.f};
-        if (r < static_cast<int>(p->run_route.size()) && p->run_route[r]) {   // PCG: statistics, Gram, iterations
-            for (int k = 2; k < DBSLMM_K_COUNT; ++k) span[k] = 0.f;
-            span[DBSLMM_K_PCG] = t[7] - t[2];
-            span[DBSLMM_K_PCG_BLOCK] = t[4] - t[3];   // (inside the PCG span, on the second stream)
-        }
         for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
         // the lead group's Gram (9 -> 10) sits inside the statistics span (0 -> 1)
         float lg = 0.f;
@@ -2256,6 +2268,11 @@ static int pcg_layout(dbslmm_plan* p, int n) {
     p->n_pblk = static_cast<int32_t>(blk.size());
     p->n_pitem = static_cast<int32_t>(items.size());
     p->n_prow = static_cast<int32_t>(rows.size());
+    // past the tile rows, one header entry per block solved whole: a trimmed dbslmm_pcg_init (run_pcg)
+    // runs the chip-wide blocks' tile rows and these
+    for (int b = 0; b < static_cast<int>(blk.size()); ++b)
+        if (blk[b].fused) rows.push_back(int2{b, -1});
+    p->n_phead = static_cast<int32_t>(rows.size()) - p->n_prow;
     p->pcg_vstride = vo;
     p->h_pmat = mat;
     p->h_ppart = part;
@@ -2451,20 +2468,23 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     p->pcg_ev_end = ev ? ev[7] : nullptr;
     p->trsv_failed = false;
     p->stopped = false;
-    const size_t nbk = static_cast<size_t>(p->nbk);
-    HIP_TRY(ctx, hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), s));
-    HIP_TRY(ctx, hipMemsetAsync(p->d_status, 0, n * nbk * sizeof(int32_t), s));
-    HIP_TRY(ctx, hipMemsetAsync(p->d_pact, 0, sizeof(int32_t), s));
     if (ev) HIP_TRY(ctx, hipEventRecord(ev[0], s));
-    for (int c = 0; c < n; ++c)
-        hipLaunchKernelGGL(dbslmm_set_scalar, dim3(1), dim3(1), 0, s, p->d_dshift + c,
-                           1.0 / (sigmas[c] * static_cast<double>(p->n_obs)));
-    if (p->n_slots > 0)
-        hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, s, p->img.rows(),
-                           p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
-                           p->d_flags);
+    // One launch in front of the Gram: the statistics, and with them the run's resets (status,
+    // the count of iterating blocks, dbslmm_pcg_block's sequence counter) and the copies' shifts.
+    // The timed instants of this route are events 0, 1, 2, 3, 4 and 7 (collect_timing).
+    static_assert(pcg::kMaxNC <= kFrontCopies, "PcgFront carries every copy's shift");
+    PcgFront fr{};
+    for (int c = 0; c < n; ++c) fr.shift[c] = 1.0 / (sigmas[c] * static_cast<double>(p->n_obs));
+    fr.dshift = p->d_dshift;
+    fr.n = n;
+    fr.n_status = static_cast<int32_t>(n * p->nbk);
+    fr.status = p->d_status;
+    fr.active = p->d_pact;
+    fr.next = p->n_pflist > 0 ? p->d_pfnext : nullptr;
+    hipLaunchKernelGGL(dbslmm_pcg_front, dim3(std::max(1, (p->n_slots + 255) / 256)), dim3(256), 0, s, p->img.rows(),
+                       p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd, p->d_flags, fr);
     HIP_TRY(ctx, hipGetLastError());
-    if (ev) for (int k : {1, 9, 10}) HIP_TRY(ctx, hipEventRecord(ev[k], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));
     uint16_t* g16 = p->pcg_g16 ? p->d_G16 : nullptr;
     const double nrd = static_cast<double>(p->n_ref), padk = static_cast<double>(p->kpad - p->n_ref);
     // the Gram of tile lists (i8, big, huge) on stream st
@@ -2491,7 +2511,7 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     // beside the chip-wide iterations -- its 256-tile workgroups hold 128 KiB of LDS, so the product
     // items cannot run beside them: config 4 8.8 -> 9.6 ms.)
     HIP_TRY(ctx, gram(s, p->d_tiles, p->n_tiles, p->d_btiles, p->n_btiles, p->d_htiles, p->n_htiles));
-    if (ev) for (int k : {2, 5, 6, 8, 11}) HIP_TRY(ctx, hipEventRecord(ev[k], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[2], s));
     PcgArgs a{};
     a.blk = p->d_pblk;
     a.G16 = g16;
@@ -2546,7 +2566,14 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     for (int c = 1; c < n; ++c)
         if (sigmas[c] > sigmas[a.seed]) a.seed = c;
     p->pcg_args = a;
-    hipLaunchKernelGGL(dbslmm_pcg_init, dim3(p->n_prow), dim3(pcg::kThreads), 0, s, a, p->d_prow);
+    // Once a run has read the missing-call flags and none of the blocks dbslmm_pcg_block takes has
+    // any (pcg_trim), those blocks keep their whole state in LDS: their tile rows' vectors are
+    // neither written nor read, and one header workgroup each does what their tile row 0 did.
+    if (p->pcg_trim)
+        hipLaunchKernelGGL(dbslmm_pcg_init, dim3(std::max(1, p->n_prow_chip + p->n_phead)), dim3(pcg::kThreads), 0, s, a,
+                           p->d_prow, p->n_prow_chip, p->n_prow - p->n_prow_chip);
+    else
+        hipLaunchKernelGGL(dbslmm_pcg_init, dim3(p->n_prow), dim3(pcg::kThreads), 0, s, a, p->d_prow, p->n_prow, 0);
     HIP_TRY(ctx, hipGetLastError());
     p->pcg_join = false;
     if (p->n_pflist > 0) {   // the small blocks' whole solves beside the chip-wide iterations
@@ -2556,8 +2583,8 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
         // one workgroup per CU (its LDS holds x and p: one fits): the chip-wide kernels of the
         // other blocks keep the rest of every CU
         // (two per CU at one copy, where their LDS fits: configs 3 / 5 6.02 -> 6.27 / 2.35 -> 2.51 ms)
-        const int grid = std::max(1, std::min(p->n_pflist, ctx->n_cu));
-        HIP_TRY(ctx, hipMemsetAsync(p->d_pfnext, 0, 16, ctx->stream2));
+        int grid = std::max(1, std::min(p->n_pflist, ctx->n_cu));
+        if (p->pcg_block_wgs > 0) grid = std::min(grid, p->pcg_block_wgs);
         hipLaunchKernelGGL(dbslmm_pcg_block, dim3(grid), dim3(pcg::kThreads), pcg::block_lds_bytes(n), ctx->stream2, a,
                            p->d_pflist, p->n_pflist, p->d_pfnext, p->pcg_maxit);
         HIP_TRY(ctx, hipGetLastError());

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 18
+#define DBSLMM_ABI_VERSION 19
 
 enum {
     DBSLMM_OK = 0,
@@ -154,6 +154,10 @@ typedef struct dbslmm_plan dbslmm_plan;
  *                factorisation route, plan_run + plan_download and multi-device contexts always
  *                are.  Bit-identical results either way.  (The Python binding passes an explicit
  *                stream_out = 0 as -1, so there 1 / 0 read on / off.)
+ * pcg_block_wgs  PCG (ABI 19): at most this many workgroups of dbslmm_pcg_block (each takes its
+ *                sequences from one counter, so the results are bit-identical for any value); 0 =
+ *                default, one per compute unit (never more than there are sequences or compute
+ *                units).
  */
 typedef struct dbslmm_options {
     int32_t tiled_min;
@@ -176,6 +180,7 @@ typedef struct dbslmm_options {
     int32_t pcg_maxit;
     int32_t pcg_whole;
     int32_t stream_out;
+    int32_t pcg_block_wgs;
 } dbslmm_options;
 
 /* One LD-block problem set, the arguments of DBSLMMFIT::est in flat form.
