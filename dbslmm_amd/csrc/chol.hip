@@ -570,6 +570,7 @@ constexpr int kChebLdsDoubles = 5 * kChebR * kChebMaxM + kTileD + kChebR * (kChe
 // (lambda_min >= fs[q] = d_c + 1 - tau without large SNPs, fl = 1 - tau with), `iters` the cap.
 struct CgStop {
     int32_t on;
+    int32_t capped;   // `iters` is a cap that pcg_maxit cut below the a priori count (cheb_plan)
     double fs[kChebR];
     double fl;
     double tol;
@@ -818,8 +819,9 @@ extern "C" __global__ __launch_bounds__(chol::kChebThreads) void dbslmm_chol_che
         }
         __syncthreads();
         const uint32_t open = cheb_block(M_base + blk_matoff[b], ld, m, ms, nr, iters, coef, lds, cgs);
-        // CG reached its cap (the Chebyshev count) above the bound: reported, not silent
-        if (tid < nr && (open >> tid & 1u))
+        // CG reached a cap lowered below the a priori count above the bound: reported, not silent
+        // (VERDICT r05); after the full count the a priori bound holds (cheb_plan)
+        if (cgs.capped && tid < nr && (open >> tid & 1u))
             status[(tid == 0 ? c0 : c1) * st_stride + blk_id[b]] = DBSLMM_BLOCK_NOT_CONVERGED;
     }
     for (int e = tid; e < nr * m; e += kChebThreads) {

@@ -1783,6 +1783,7 @@ struct ChebPlan {
     double db = 0.0;                  // the base copy's shift d_b = 1 / (sigma_b n)
     std::vector<int> others;          // copies solved by iteration, in launch groups of kMaxR
     std::vector<int> iters;           // per group
+    std::vector<char> capped;         // per group: pcg_maxit cut CG's cap below the a priori count
     std::vector<double> coef;         // per group: [iters][nr][3] {alpha, beta, delta}
     std::vector<size_t> coef_off;
 };
@@ -1823,14 +1824,25 @@ static bool cheb_plan(const dbslmm_plan* p, const double* sigmas, int n, ChebPla
             // at h2f 0.8 / 1 / 1.2, measured error ~0.2 x the target)
             const double kap = hi[j] / lo[j], q = (std::sqrt(kap) - 1.0) / (std::sqrt(kap) + 1.0);
             const double e0 = std::max(std::fabs(ext), 1e-300);
-            const int k = q < 1e-300 ? 1 : std::max(1, static_cast<int>(std::ceil(std::log(tol / e0) / std::log(q))));
+            // (2 q^K e0 <= tol, the 2 included: without it the count came out one short wherever
+            // log(tol / e0) / log q fell within log 2 / |log q| below an integer, and the copies of
+            // h2f 0.5 on a base of 1.0 / 1.3 measured 1.2e-9 / 1.35e-9 per block -- the bound's own
+            // value at that count -- against the target of 1e-9)
+            const int k = q < 1e-300 ? 1
+                                     : std::max(1, static_cast<int>(std::ceil(std::log(tol / (2.0 * e0)) / std::log(q))));
             K = std::max(K, k);
         }
         if (K > 60) return false;
-        // CG (h2f_iter 2) iterates adaptively with the Chebyshev count as its cap; pcg_maxit lowers
-        // that cap (tests drive a copy to it: DBSLMM_BLOCK_NOT_CONVERGED)
-        if (p->h2f_cg && !p->cheb_fused) K = std::min(K, p->pcg_maxit);
+        // CG (h2f_iter 2) iterates adaptively with the Chebyshev count as its cap.  A copy that ran
+        // all K iterations is within the target whatever its stopping test says: 2 q^K e_0 <=
+        // cheb_tol holds on an interval that does not depend on the data, and CG's energy-norm
+        // error is at most Chebyshev's.  (The stopping test cannot say so at tau = 1: its
+        // lambda_min bound of a block with large SNPs, 1 - tau, is 0.)  Only a cap that pcg_maxit
+        // cut below K can leave a copy short of the target: DBSLMM_BLOCK_NOT_CONVERGED
+        const bool capped = p->h2f_cg && !p->cheb_fused && p->pcg_maxit < K;
+        if (capped) K = p->pcg_maxit;
         cp.iters.push_back(K);
+        cp.capped.push_back(capped);
         cp.coef_off.push_back(cp.coef.size());
         std::vector<double> rho(nr);
         for (int k = 0; k < K; ++k)
@@ -2039,6 +2051,7 @@ static int run_cheb(dbslmm_plan* p, double isn, const ChebPlan& cp, const TGroup
                 }
                 ca.floor_l = 1.0 - p->tau;
                 ca.tol = p->h2f_tol;
+                ca.capped = cp.capped[g];
                 ca.rec = p->d_cgrec;
                 ca.conv = p->d_cgconv;
                 ca.iters = p->d_cgit;
@@ -2805,6 +2818,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                 for (int j = 0; j < nr; ++j) cgs.fs[j] = cp.db + cp.coef[cp.coef_off[g] + 3 * j + 2] + 1.0 - p->tau;
                 cgs.fl = 1.0 - p->tau;
                 cgs.tol = p->h2f_tol;
+                cgs.capped = cp.capped[g];
                 hipLaunchKernelGGL(dbslmm_chol_cheb, dim3(p->n_large), dim3(chol::kChebThreads), kCholChebLds, s,
                                    p->d_M + bc * p->M_elems, p->d_order, p->n_large, p->d_row0, p->d_m, p->d_ms,
                                    p->d_ld, p->d_matoff, p->d_blk_id, p->d_slot_out, p->d_y + bc * p->n_slots,

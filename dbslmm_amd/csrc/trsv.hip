@@ -519,9 +519,11 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_cheb_init(
 // 1 + delta / (d_b + 1 - tau)], not the a priori [1, ...] the Chebyshev coefficients must cover),
 // so it stops early: after each update a copy has converged when |r| <= cheb_tol lambda_min(M_c)
 // |x| (a bound on the relative error, lambda_min(M_c) >= d_c + 1 - tau, or 1 - tau for a block
-// with large SNPs).  A block whose copies have all converged writes its betas and sets conv[b]:
-// the later passes skip its items (tools/cheb_vs_cg.py: 5 iterations on config 4's blocks of
-// 544 - 9667 SNPs where Chebyshev needs 7; the a priori Chebyshev count stays the cap).
+// with large SNPs: 0 at tau = 1, where such a block runs the whole a priori count and is within
+// the target by that count's own bound).  A block whose copies have all converged writes its
+// betas and sets conv[b]: the later passes skip its items (tools/cheb_vs_cg.py: 5 iterations on
+// config 4's blocks of 544 - 9667 SNPs where Chebyshev needs 7; the a priori Chebyshev count
+// stays the cap).
 // One workgroup per tiled block of the group, after each backward pass; reductions in a fixed
 // order (deterministic).
 namespace trsv {
@@ -535,6 +537,7 @@ struct CGArgs {
     const int32_t* slot_out;
     const int32_t* st_base;      // the base copy's block status
     int32_t nr, k, last;
+    int32_t capped;              // pcg_maxit cut the cap below the a priori count (cheb_plan)
     int64_t vs;
     const double* Z;             // z = M_b^{-1} r (the backward pass's result)
     double* X;
@@ -553,7 +556,7 @@ struct CGArgs {
     double* beta_l;
     int64_t ns_stride, nl_stride;
     int32_t cix[kMaxR];
-    int32_t* status;             // per copy (cix) and original block: NOT_CONVERGED at the cap
+    int32_t* status;             // per copy (cix) and original block: NOT_CONVERGED at a lowered cap
     int64_t st_stride;
 };
 // sums of v[0..4) over the workgroup, in a fixed order; every thread gets the totals
@@ -639,9 +642,11 @@ extern "C" __global__ __launch_bounds__(trsv::kCGThreads) void dbslmm_cg_update(
         const double t = a.tol * (ms == m ? a.floor_s[c] : a.floor_l);
         const bool cc = w[2 * c] <= t * t * w[2 * c + 1];   // NaN: not converged
         conv = conv && cc;
-        // the cap (the Chebyshev count) reached without the bound: the copy keeps this iterate and
-        // reports it (the cap was silent); a failed base factor keeps its own status
-        if (a.last && !cc && !fail && tid == 0 && a.status)
+        // a cap lowered below the a priori count reached without the bound: the copy keeps this
+        // iterate and reports it (the cap was silent); after the full count the copy
+        // is within the target by the a priori bound (cheb_plan); a failed base factor keeps its
+        // own status
+        if (a.last && a.capped && !cc && !fail && tid == 0 && a.status)
             a.status[a.cix[c] * a.st_stride + a.blk_id[b]] = DBSLMM_BLOCK_NOT_CONVERGED;
     }
     const bool done = a.last || fail || conv;
@@ -845,6 +850,10 @@ __global__ __launch_bounds__(trsv::kBThreads, 2) void dbslmm_tcheb(TChebArgs a) 
         a.D[o] = 0.0;
         a.S[o] = 0.0;
     }
+    // r of copy c > 0 is loaded below by other threads than wrote it here (e = c m + i there,
+    // c vld + i here): without this barrier the first pass of the second copy read whatever the
+    // last run left in R wherever m < vld
+    __syncthreads();
     for (int k = 0; k < a.iters && !fail; ++k) {
         for (int e = tid; e < NR * a.vld; e += kBThreads) {
             const int c = e / a.vld, i = e - c * a.vld;

@@ -52,8 +52,13 @@ enum {
                                       meeting its error bound: beta = the last iterate (the
                                       reference's PCG prints "Matrix is Singular!" at maxiter and
                                       returns its iterate, dbslmmfit.cpp:664-666).  The PCG route
-                                      (solver, pcg_maxit) and the h2f copies iterated on a base
-                                      factor (h2f_iter: CG / Chebyshev at their caps) report it. */
+                                      (solver, pcg_maxit) reports it, and so does an h2f copy
+                                      iterated by CG on a base factor (h2f_iter) when pcg_maxit
+                                      cut its cap below the a priori count and the copy was still
+                                      above its bound there.  A copy that ran the whole a priori
+                                      count is OK: the count itself bounds its error by cheb_tol
+                                      (at tau = 1 the stopping test of a block with large SNPs,
+                                      |r| <= cheb_tol (1 - tau) |x|, can never pass). */
 };
 
 typedef struct dbslmm_ctx dbslmm_ctx;
@@ -118,9 +123,13 @@ typedef struct dbslmm_plan dbslmm_plan;
  *                (a priori coefficients and iteration count), 2 = preconditioned CG on the same
  *                factor (Chronopoulos-Gear form, dbslmm_cg_update / dbslmm_chol_cheb): stops per
  *                block once |r| <= cheb_tol lambda_min(M_c) |x|,
- *                capped at the Chebyshev count (a copy still above the bound there is reported
- *                DBSLMM_BLOCK_NOT_CONVERGED); 0 = the default (2).  Both within cheb_tol; the
- *                base copy is bit-identical either way.  (cheb_fused = 1 and the whole-block rest
+ *                capped at the Chebyshev count K (2 q^K e_0 <= cheb_tol on an interval that does
+ *                not depend on the data; CG's energy-norm error is at most Chebyshev's, so a copy
+ *                that ran all K iterations is within the target and OK whether or not the stopping
+ *                test passed -- with large SNPs and tau = 1 its bound is 0 and the block always
+ *                runs K).  Only when pcg_maxit lowered the cap below K is a copy still above the
+ *                bound there reported DBSLMM_BLOCK_NOT_CONVERGED; 0 = the default (2).  Both
+ *                within cheb_tol; the base copy is bit-identical either way.  (cheb_fused = 1 and the whole-block rest
  *                group of sub_split = 2 iterate by Chebyshev.)
  * solver         how a run solves its blocks (ABI 12): 1 = factorisation (fp64 Cholesky of every
  *                block, the paths above); 2 = PCG: the reference's own algorithm (Jacobi-PCG,
