@@ -49,11 +49,13 @@ namespace var {
 constexpr int kRhs = 64;      // test individuals per workgroup
 constexpr int kChunk = 32;    // rows per substitution chunk
 
-// standardised test genotype of slot s for individual t (missing -> the mean -> 0)
+// standardised test genotype of slot s for individual t (missing -> the mean -> 0, times 1/sd as
+// nomalizeVec divides every entry: NaN for a SNP without variance among the selected individuals
+// (1/sd = inf) or without an observed call (readSNPIm's mean is 0/0, 1/sd = NaN), +0 otherwise)
 __device__ __forceinline__ double xval(const uint8_t* cbed, int64_t cpitch, const double* mu,
                                        const double* rsd, int s, int t) {
     const uint32_t code = (static_cast<uint32_t>(cbed[static_cast<int64_t>(s) * cpitch + (t >> 2)]) >> (2 * (t & 3))) & 3u;
-    if (code == 1u) return 0.0;
+    if (code == 1u) return 0.0 * rsd[s];
     const double g = code == 0 ? 2.0 : (code == 2 ? 1.0 : 0.0);
     return (g - mu[s]) * rsd[s];
 }

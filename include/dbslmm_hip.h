@@ -422,7 +422,9 @@ typedef struct dbslmm_test_panel {
 /* After plan_run / plan_run_multi (uses the factorisation of the most recent sigma_s):
  * diags is n_test x num_block column-major, n_test = number of indicator entries equal to 1;
  * column b = diag(X_l var_bl X_l^T + X_s var_bs X_s^T) of block b, zeros for a block without
- * SNPs, NaN for a block whose status is NOT_PD / MONOMORPHIC.  Synchronous; host buffers.
+ * SNPs (a block of large SNPs only: x_l^T Sigma_ll^-1 x_l / n), NaN for a block whose status is
+ * NOT_PD / MONOMORPHIC and, as in the reference, for a block with a test SNP that has no variance
+ * or no observed call among the selected individuals.  Synchronous; host buffers.
  * n_test_out (optional) receives n_test. */
 int dbslmm_plan_variance(dbslmm_plan* plan, const dbslmm_test_panel* test, double* diags,
                          int32_t* n_test_out);

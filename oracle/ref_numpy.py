@@ -564,7 +564,7 @@ def nt_diag_s(sigma_ss, sigma2_s, n, Xs_test):
 
 def block_sigmas(Xs, Xl, n_ref, tau=0.8):
     """Sigma_ss, Sigma_sl, Sigma_ll of estBlock (dbslmmfit.cpp:698-709), diagonal restored."""
-    ss = tau * Xs.T @ Xs / n_ref + (1 - tau) * np.eye(Xs.shape[1])
+    ss = tau * Xs.T @ Xs / n_ref + (1 - tau) * np.eye(Xs.shape[1])   # (0 x 0 for a block of large SNPs only)
     if Xl is None or Xl.shape[1] == 0:
         return ss, None, None
     sl = tau * Xs.T @ Xl / n_ref
@@ -575,7 +575,9 @@ def block_sigmas(Xs, Xl, n_ref, tau=0.8):
 def variance_diags(bed, n_ref, n_obs, sigma_s, num_block, info_s, info_l, test_bed, indicator,
                    test_info_s, test_info_l, tau=0.8):
     """The diags matrix of DBSLMMFIT::est (dbslmmfit.cpp:116, 191-214, 242): n_test x num_block,
-    column b = calcBlock's variance diag (zeros for a block without SNPs)."""
+    column b = calcBlock's variance diag (zeros for a block without SNPs).  A block of large SNPs
+    only goes through the large+small formulas with empty small-SNP matrices, as calcBlock does:
+    x_l^T Sigma_ll^-1 x_l / n."""
     n_test = int(indicator.sum())
     diags = np.zeros((n_test, num_block))
     for b in range(num_block):
@@ -583,7 +585,7 @@ def variance_diags(bed, n_ref, n_obs, sigma_s, num_block, info_s, info_l, test_b
         rl = [x["pos"] for x in (info_l or []) if x["block"] == b]
         ts = [x["pos"] for x in test_info_s if x["block"] == b]
         tl = [x["pos"] for x in (test_info_l or []) if x["block"] == b]
-        if not rs:
+        if not rs and not rl:
             continue
         Xs = read_block_matrix(bed, rs, n_ref)
         Xs_t = read_test_block_matrix(test_bed, ts[:len(rs)], indicator)

@@ -228,13 +228,15 @@ def synth_variance_case(seed=3, n_ref=300, n_total=150, mono_block=None):
 
 
 def synth_oracle(prob, tbed, ind, ts_pos, tl_pos, sigma=None):
-    """The literal formulas per block at the problem's tau (0.8 unless the case sets another)."""
+    """The literal formulas per block at the problem's tau (0.8 unless the case sets another); a
+    block of large SNPs only through the large+small formulas with empty small-SNP matrices
+    (x_l^T Sigma_ll^-1 x_l / n), only a block without any SNP is a zero column."""
     sigma = prob.sigma_s if sigma is None else sigma
     D = np.zeros((int(ind.sum()), prob.num_block))
     for b in range(prob.num_block):
         rs = prob.s_pos[prob.s_ptr[b]:prob.s_ptr[b + 1]]
         rl = prob.l_pos[prob.l_ptr[b]:prob.l_ptr[b + 1]]
-        if rs.size == 0:
+        if rs.size == 0 and rl.size == 0:
             continue
         Xs = R.read_block_matrix(prob.bed, rs, prob.n_ref)
         Ts = R.read_test_block_matrix(tbed, ts_pos[prob.s_ptr[b]:prob.s_ptr[b + 1]], ind)
