@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dims.hpp"
+
 namespace chol {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
@@ -32,7 +34,6 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 constexpr int kWave = 64;
 constexpr int kT = 32;          // tile edge
 constexpr int kTS = 34;         // LDS row stride of MFMA operand tiles (conflict-free 16x4 reads)
-constexpr int kSmallLd = 64;    // small path: ld <= 64 (m <= 63)
 constexpr int kSmallWaves = 2;  // small kernel: 2 waves (blocks) per workgroup
 constexpr int kSmallTri = kSmallLd * (kSmallLd + 1) / 2;   // packed bordered triangle
 constexpr int kSmallDoublesPerWave = kSmallTri + kSmallLd;  // + reciprocal pivots
@@ -560,7 +561,6 @@ __device__ void large_block(const BlockArgs& a, double* __restrict__ M, double* 
 // two more copies (2 m^3 / 3 flops, the whole matrix written twice) becomes ~16 triangular
 // passes (~8 m^2 flops) with far less LDS per workgroup, so several blocks share a CU.
 constexpr int kChebR = 2;                           // copies per launch group (trsv::kMaxR)
-constexpr int kChebMaxM = 512;                      // ld > 64 blocks are below the tiled threshold
 constexpr int kChebThreads = 512;                   // one strip row / column per thread (m <= 512)
 constexpr int kChebLdsDoubles = 5 * kChebR * kChebMaxM + kTileD + kChebR * (kChebThreads / kT) * kT;
 

@@ -1,7 +1,7 @@
 // chol_tiled.hip -- multi-workgroup Cholesky + solves for the big LD blocks (included by plan.hip
 // after chol.hip).  Same bordered system as chol.hip (z appended as row m, y = L^{-1} z left in
 // row m, beta = L^{-T} y / sqrt n), but every block with m >= the tiled threshold is spread over
-// many workgroups, batched across blocks, one launch per phase (schedule: build_tiled in plan.hip):
+// many workgroups, batched across blocks, one launch per phase (schedule: build_tiled in plan_layout.hpp):
 //
 //   tchol_region        factor + invert a 128 x 128 diagonal region in LDS (+ pending updates)
 //   tchol_panel         L_i = A_i L_RR^{-T} per 64-row tile below the region (+ pending update)
@@ -17,9 +17,10 @@
 //
 // Work items of the region / panel / trailing launches are int32 pairs [block or tile,
 // (local step << 8) | count]: every block runs at its own step inside a shared launch.
+#include "dims.hpp"
+
 namespace chol {
 
-constexpr int kBT = 64;                          // tiled-path tile edge (half the panel width)
 constexpr int kSub = kT * kTS;                   // one 32x32 LDS sub-tile (stride 34)
 // LDS carve of the tiled kernels (doubles): 8 sub-tiles = two 64x64 operands
 constexpr int kTiledDoubles = 8 * kSub + 2 * kT + 8;
@@ -627,8 +628,6 @@ extern "C" __global__ __launch_bounds__(chol::kLargeThreads, 2) void dbslmm_tcho
 namespace chol {
 constexpr int kT2 = 128;                 // tile edge
 constexpr int kK2 = 32;                  // K per stage
-constexpr int kRun2 = 1;                 // tiles per run (2 measured slower with two workgroups per CU:
-                                         // trail_bench m 9596 K 512, 63.5 vs 73.5 % of the f64 peak)
 }  // namespace chol
 
 // The same update fed by LDS-DMA (global_load_lds_dwordx4): no staging registers, no LDS store

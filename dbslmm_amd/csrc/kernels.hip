@@ -35,13 +35,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dims.hpp"
+
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int kWave = 64;
-constexpr int kTile = 32;          // gram / cholesky tile edge (SNP slots)
 constexpr int kLdsStride = 33;     // padded LDS row stride (doubles) -> conflict-free column reads
 
 __device__ __forceinline__ void wave_sync() {
@@ -415,8 +416,6 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_maf_arma(
 // Output: row-major lower triangle of the block's joint matrix
 //     Sigma (no d shift; the Cholesky kernel adds 1/(sigma_s n) on the small diagonal).
 // ------------------------------------------------------------------------------------------
-struct GramTile { int32_t block, ti, tj, pad; };
-
 // Factorisation copies an epilogue writes (h2f tuning): copies [0, ncopy) of every block, except
 // that with tcopy >= 0 a tiled block (m >= tmin) gets copy tcopy only -- the other h2f solves of
 // the tiled blocks iterate on that one factor (trsv.hip) and need no matrix of their own.
@@ -553,7 +552,6 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_i8(
 // by the statistics pass) take the exact 4-product 32 x 32 path.
 // ------------------------------------------------------------------------------------------
 namespace gram {
-constexpr int kGT = 128;                  // output tile edge
 constexpr int kKS = 256;                  // individuals per K stage
 constexpr int kRS = kKS / 2 + 16;         // LDS row stride (bytes): 128 B of FP4 codes + pad
 constexpr int kOpBytes = kGT * kRS;       // one operand stage
@@ -737,10 +735,9 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_gram_big(
 // tiles) are skipped.  Missing-call blocks: the exact 4-product path per 32 x 32 sub-tile.
 // ------------------------------------------------------------------------------------------
 namespace gram {
-constexpr int kHT = 256;                   // output tile edge
 constexpr int kHK = 256;                   // individuals per K stage (64 B of 2-bit codes per row)
 constexpr int kHLdsBytes = 4 * 2 * kHT * (kHK / 4);   // 4 DMA slots x (A | B) x 16 KiB = 128 KiB
-constexpr int kKpadAlign = kHK;            // kpad: a multiple of the stage
+static_assert(kKpadAlign == kHK, "kpad: a multiple of the stage");
 }  // namespace gram
 
 // K loop of dbslmm_gram_huge fed by LDS-DMA.  A stage (256 individuals) of a tile row is 64 B of

@@ -59,7 +59,7 @@ constexpr int kH2fIters = 6;               // h2f {0.8, 1, 1.2} at cheb_tol 1e-9
                                             // rates fitted before CG: the rehearsal's devices within
                                             // 21.5-22.1 (N = 4) / 15.0-15.8 ms (N = 8) where 5 left the
                                             // whole-block devices 1.1-1.3 ms behind (profiles/r05/cg)
-constexpr int kTiledMin = 384;              // plan.hip kTiledMinDefault
+constexpr int kTiledMin = 384;              // plan_layout.hpp kTiledMinDefault
 
 struct Cost {
     double work = 0.0;    // chip-ms
@@ -659,7 +659,7 @@ static int mp_run(dbslmm_plan* p, const double* sigmas, int n, bool wait) {
         }
         std::vector<double> sg;
         for (int c : sh.run_copies) sg.push_back(sigmas[c]);
-        int r = run_impl(sh.plan, true, sg.data(), static_cast<int>(sg.size()));
+        int r = run_impl(sh.plan, sg.data(), static_cast<int>(sg.size()));
         if (r == DBSLMM_OK && wait) r = dbslmm_plan_sync(sh.plan);
         return r;
     });

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <numeric>
 #include <string>
 #include <memory>
@@ -39,6 +40,7 @@
 
 #include "../../include/dbslmm_hip.h"
 #include "out_ranges.hpp"
+#include "plan_layout.hpp"
 
 // The kernels are compiled in this translation unit (no relocatable device code needed).
 #include "kernels.hip"
@@ -50,52 +52,38 @@
 #include "pcg.hip"
 
 namespace {
-// events per timed run: [0] start, [1] after the statistics gather (slot name: unpack), [2] after gram, [3] after chol_large,
-// [4] / [5] around chol_small (main stream), [6] / [8] around the tiled factorisation sequence,
-// [8] / [7] around the h2f Chebyshev iterations (stream2)
-constexpr int kEvPerRun = 12;   // 9, 10: around the lead group's Gram (between the statistics and [1]);
-                                // 11: the rest group's factorisation + backward done (its own
-                                // stream, split substitutions; else recorded with 8)
+// the instants of a timed run, one event each (collect_timing turns them into kernel spans)
+enum Ev {
+    kEvStart,           // the run's start
+    kEvStatsEnd,        // after the statistics gather (slot name: unpack) and the lead group's Gram
+    kEvGramEnd,         // after the Gram
+    kEvLargeEnd,        // after chol_large
+    kEvSmallBegin,      // around chol_small (the main stream, or stream2 without a tiled sequence)
+    kEvSmallEnd,
+    kEvTiledBegin,      // the tiled factorisation sequence starts (stream2)
+    kEvEnd,             // the h2f Chebyshev iterations are done (stream2); PCG: its iterations
+    kEvTiledEnd,        // the tiled factorisation + backward are done and the h2f Chebyshev iterations
+                        // start (stream2; split substitutions: the lead group's)
+    kEvLeadGramBegin,   // around the lead group's Gram (between the statistics and kEvStatsEnd)
+    kEvLeadGramEnd,
+    kEvRestEnd,         // the rest group's factorisation + backward done (its own stream, split
+                        // substitutions; else recorded with kEvTiledEnd)
+    kEvCount,           // events per timed run
+    kEvPcgBlockBegin = kEvLargeEnd,   // PCG route: around dbslmm_pcg_block (stream2)
+    kEvPcgBlockEnd = kEvSmallBegin,
+};
+// every instant after the Gram, in stream order: what a run that ends there (no blocks, debug_stop) records
+constexpr std::initializer_list<Ev> kEvAfterGram = {kEvLargeEnd, kEvSmallBegin, kEvSmallEnd, kEvTiledBegin,
+                                                    kEvTiledEnd, kEvRestEnd, kEvEnd};
 constexpr size_t kCholLargeLds = sizeof(double) * chol::kLargeDoubles;
 constexpr size_t kCholChebLds = sizeof(double) * chol::kChebLdsDoubles;
 constexpr size_t kTiledLds = sizeof(double) * chol::kTiledDoubles;
 constexpr size_t kRegionLds = sizeof(double) * chol::kRegionDoubles;
 constexpr size_t kTrail3Lds = sizeof(double) * chol::kTrail3k16Doubles;   // the K = 16 variant (2 per CU)
-constexpr int kTiledMinDefault = 384;   // blocks with m >= this take the multi-workgroup path
-                                        // (round 4, with the per-group substitutions: config 4
-                                        // 44.1-44.3 -> 43.2-43.3 ms, one run in four 45.0; configs
-                                        // 3 / 5 -0.1 / -0.2 ms; 512 before, 320 no better)
-constexpr int kTiledMinSmall = 256;     // the same when no block reaches 512 SNPs (config 2)
 constexpr int kBedPad = 64;            // zero bytes after a verbatim .bed upload (dbslmm_bed_repitch reads whole 16-B chunks)
-constexpr int kGramBigMinDefault = 96;  // blocks with m >= this take the 128 x 128 Gram kernel
-constexpr int kGramHugeMinDefault = 384; // ... and the 256 x 256 one from here (swept: configs 3, 5)
-constexpr int kTChebMaxM = 4096;         // whole-block Chebyshev passes: blocks of <= 64 tiles
-constexpr int kLeadMinDefault = 1536;    // lead group: m >= max(this, m_max / 8) (dbslmm_options.lead_min)
-constexpr int kXcd = 8;                 // workgroup id e runs on XCD e % 8
 constexpr int kEpochsPerRun = 1 << 14;  // substitution epochs one run may take (next_epoch)
 
-// one launch of the tiled sequence: the active blocks and the prefix of their work items
-struct TLaunch {
-    int kind;         // 1 panel, 4 region, 5 trailing (128 x 128 tiles); items are int32 pairs
-                      // carrying each block's own step
-    int step;
-    int32_t off;      // into d_tlist: act[n] then pfx[n + 1]
-    int32_t n;
-    int32_t items;    // workgroups
-    int32_t nk = 1;   // trailing: K = 128 nk (regions step .. step+nk-1); region: pending panels
-    int strm = 0;     // 0: the sequence's chain stream, 1: its bulk-trailing stream
-};
-// sync entries of a launch list (lookahead): kind 6 records tiled event `step` on stream `strm`,
-// kind 7 makes stream `strm` wait for it
-constexpr int kTlRecord = 6, kTlWait = 7;
-constexpr int kSuper = 2;               // regions (128 columns) per super step
-constexpr int kWideSuper = 4;           // ... for blocks of m >= kWideMin (half the C traffic per
-constexpr int kWideMin = 4096;          //     flop; config 5 35.4 -> 34.3 ms/step)
-constexpr int kTiledMaxM = 255 * 128;   // tiled path: 128-row tile and region indices < 256
-constexpr int kGramSq = 4;              // 2D tile squares per XCD of the 256-tile Gram
-constexpr int kTrailSq = 8;             // 2D squares (in 128-tiles) per XCD of the trailing update
-
-int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+static_assert(sizeof(v4i) == kRowEntryBytes, "one row-table entry");
 // The resident panel image (kernels.hip: dbslmm_bed_repitch): n_rows rows of `pitch` bytes and the
 // zero-dosage row n_rows, made for n_ref individuals, followed IN THE SAME ALLOCATION by the row
 // table: one 16-byte entry {sum, sumsq, nmiss, 0} per row (the zero-dosage row's all zero), the
@@ -169,37 +157,26 @@ struct dbslmm_mplan {
     std::vector<int32_t> unit_device;   // [block * n_copies + copy] -> device index, -1 empty
 };
 
-struct dbslmm_plan {
+// (the host layout plan_create computed lives in the base: plan_layout.hpp)
+struct dbslmm_plan : PlanLayout::Kept {
     dbslmm_ctx* ctx = nullptr;
     dbslmm_mplan* mp = nullptr;        // multi-device plan: every call fans out over its shards
     int32_t n_ref = 0, n_obs = 0, num_block = 0;
     double sigma_s = 0.0, tau = 0.8;
-    int64_t n_s = 0, n_l = 0, kpad = 0, bed_len = 0;
-    int32_t n_slots = 0, n_nonempty = 0, n_tiles = 0;
-    int64_t M_elems = 0;
+    int64_t bed_len = 0;
     // device
     PanelImage img;                    // own upload, or the context's cached image (shared)
     const uint8_t* d_img = nullptr;    // img.mem.get(): pitch kpad / 4, zero-dosage row img.n_rows
     int32_t *d_slot_pos = nullptr, *d_slot_block = nullptr, *d_slot_out = nullptr;
     double *d_z = nullptr, *d_S = nullptr, *d_mu = nullptr, *d_rsd = nullptr, *d_y = nullptr;
     int32_t *d_flags = nullptr, *d_status = nullptr, *d_order = nullptr, *d_blk_id = nullptr;
-    int32_t n_large = 0, n_small = 0;   // Cholesky paths (ld > 64 / ld <= 64); d_order = [large | small]
-    int32_t n_tiled = 0;                // blocks on the multi-workgroup path (not in d_order)
-    int32_t* d_tlist = nullptr;         // work lists of the tiled sequence
-    std::vector<TLaunch> tl;            // the tiled sequence (of the lead group when there is one)
-    std::vector<TLaunch> tl_rest;       // the other tiled blocks' sequence (lead group only)
+    int32_t* d_tlist = nullptr;         // work lists of the tiled sequence (tl, tl_rest)
     hipGraphExec_t graph_exec = nullptr;   // captured tiled sequence
     int32_t *d_row0 = nullptr, *d_m = nullptr, *d_ms = nullptr, *d_ld = nullptr;
     int64_t* d_matoff = nullptr;
     GramTile* d_tiles = nullptr;       // 32 x 32 tiles of the small blocks (dbslmm_gram_i8)
     GramTile* d_btiles = nullptr;      // 128 x 128 tiles of the mid blocks, per-XCD queues
-    int32_t n_btiles = 0;
     GramTile* d_htiles = nullptr;      // 256 x 256 tiles of the big blocks, per-XCD queues
-    int32_t n_htiles = 0;
-    int32_t n_htiles_lead = 0;         // ... of which the first n_htiles_lead are the lead group's,
-    int32_t n_htiles_tiled = 0;        //     the first n_htiles_tiled the tiled blocks' (then the rest)
-    bool early_fork = false;           // every tiled block's Gram is in those: the tiled sequences
-                                       // may start before the other blocks' Gram
     double* d_M = nullptr;
     double *d_beta_s = nullptr, *d_beta_l = nullptr;
     double* d_dshift = nullptr;        // 1/(sigma_s n), read by the solve kernels
@@ -215,21 +192,12 @@ struct dbslmm_plan {
     int32_t var_copy = 0;              // copy holding the latest factorisation (variance)
     int32_t score_copies = 0;          // copies of the latest user run (dbslmm_plan_score)
     bool score_stale = false;          // the variance's re-solve has overwritten copy 0 of its results
-    std::vector<int32_t> h_ld;  // per non-empty block
-    std::vector<int32_t> h_m;   // per non-empty block
-    std::vector<int32_t> h_tb;  // blocks on the tiled path
-    std::vector<int32_t> h_empty;  // original ids of empty blocks
-    std::vector<int32_t> h_blk_id; // per non-empty block: its original id
-    std::vector<int64_t> h_matoff; // per non-empty block: offset of its matrix in a copy
     void* h_pin = nullptr;         // pinned landing buffer of the result downloads
     size_t h_pin_bytes = 0;
-    std::vector<int32_t> h_slot_out;  // slot -> small index s, large -1-l, padding INT32_MIN
     double sigma_run = 0.0;        // sigma_s of the factorisation held in d_M
-    // workload figures
-    double wl[DBSLMM_WORKLOAD_LEN] = {0};
     // timing
     bool timing = false;
-    std::vector<hipEvent_t> ev;  // kEvPerRun per run
+    std::vector<hipEvent_t> ev;  // kEvCount per run
     std::vector<hipEvent_t> dl_ev;   // result download: one per factorisation copy
     std::vector<hipEvent_t> tev; // dependencies between the tiled sequence's two streams
     std::vector<hipEvent_t> tev_rest;   // ... of the rest sequence
@@ -237,17 +205,13 @@ struct dbslmm_plan {
     // forward / backward dependency order, tile flags (+ ticket counter, error word) and the
     // iteration vectors [Y, Z, X, R, D, S] x kMaxR x n_slots
     int32_t *d_tri_f = nullptr, *d_tri_b = nullptr, *d_foff = nullptr, *d_tflags = nullptr, *d_tb = nullptr;
-    int32_t n_titems = 0, n_tflags = 0;
     int32_t* d_tepi = nullptr;                 // per tile: epoch of its last stored Chebyshev update
     int32_t* d_cheb_items = nullptr;           // work list of the fused Chebyshev launch (K iterations)
     int32_t n_cheb_items = 0, cheb_items_K = -1;
     int32_t trsv_epoch = 0;                  // tile-flag value of the latest substitution launch
-    int32_t tiled_min = 0;                   // blocks with m >= this are on the tiled path
     int32_t h2f_mode = 0;                    // dbslmm_options.h2f_mode
     double cheb_tol = 1e-9;                  // dbslmm_options.cheb_tol
     double h2f_tol = 1e-9;                   // the current run's target for its iterated copies (run_impl)
-    bool large_cheb_ok = true;               // dbslmm_options.large_cheb and every chol_large block
-                                             // fits dbslmm_chol_cheb (ld <= chol::kChebMaxM)
     bool cheb_fused = false;                 // dbslmm_options.cheb_fused
     bool h2f_cg = false;                     // dbslmm_options.h2f_iter: the tiled blocks' copies by CG
     double* d_cgrec = nullptr;               // CG: per non-empty block and copy {gamma, alpha}
@@ -257,15 +221,7 @@ struct dbslmm_plan {
     int32_t debug_delay_us = 0;              // dbslmm_options.debug_delay_us (tests)
     int32_t debug_stop = 0;                  // dbslmm_options.debug_stop (tests)
     int64_t n_runs = 0;                      // completed run enqueues (graphs are captured from the second)
-    // dbslmm_options.sub_split: the substitution lists are ordered [lead group | rest group], each
-    // group a contiguous item range of d_tri_f / d_tri_b and block range of d_tb
-    bool sub_split = false;
-    int32_t n_titems_lead = 0, n_tb_lead = 0, sub_grid_lead = 0, sub_grid_rest = 0;
-    // sub_split = 2: the rest group's h2f Chebyshev passes as whole-block launches (dbslmm_tcheb):
-    // its blocks, largest first, and the LDS stride of the work vector (64 x the most tiles)
-    bool sub_block = false;
-    int32_t* d_tcheb_blocks = nullptr;
-    int32_t n_tcheb = 0, tcheb_vld = 0;
+    int32_t* d_tcheb_blocks = nullptr;       // sub_block: the rest group's blocks, largest first
     bool trsv_pending = false;               // a persistent substitution ran since the last error check
     bool trsv_failed = false;                // ... and one of its hand-off waits gave up (sticky until the next run)
     unsigned long long* d_stamps = nullptr;  // diagnostic builds (DBSLMM_DIAG) only
@@ -283,8 +239,6 @@ struct dbslmm_plan {
     bool ran = false;
     bool stopped = false;          // the last run stopped after the Gram (debug_stop = 1): no betas
     int32_t m_copies = 0;          // block-matrix copies allocated in d_M (<= n_copies)
-    std::vector<int32_t> h_ms, h_row0;   // per non-empty block: small SNPs, first slot
-    bool has_large = false;        // some block has large SNPs
     // ---- PCG route (dbslmm_options.solver, pcg.hip)
     int32_t solver = 0;            // 0 auto, 1 factorisation, 2 PCG
     double pcg_tol = 1e-12;
@@ -342,7 +296,6 @@ struct dbslmm_plan {
     int32_t so_n = 0;              // copies of the latest streamed run
     int32_t so_run = 0;            // its number (per plan; flags of earlier runs never match)
     hipEvent_t so_ev = nullptr;    // after the last work a chunk enqueued
-    std::vector<OutRange> h_orange;   // per route block: its ranges of the caller's arrays
     std::vector<int2> h_pfpairs;   // the host's scan order: dbslmm_pcg_block's (route block, copy) pairs in its
                                    // list order, then the chip-wide blocks' 
     std::vector<int32_t> so_done;  // [route block * so_n + copy] = so_run once copied out
@@ -659,186 +612,6 @@ static hipError_t dev_upload(T** dst, const std::vector<T>& src, hipStream_t st)
     return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 
-// Launch list of the tiled sequence for the blocks `tb0` (plan block indices), each replicated over
-// `copies` independent factorisations (h2f tuning: item block id bq = b + c * nb addresses copy c).
-// A block's factorisation is a chain of super steps of R regions (128 columns each; R = 4 for
-// blocks of m >= kWideMin, else 2 -- a property of the block, so its factorisation does not
-// depend on the other blocks of the sequence): region(0), then per super step
-//   panel(r0) -> for r = r0+1 .. r0+R-1: region(r) [+ its pending update from panels r0 .. r-1]
-//   -> panel(r) [+ the pending update of its rows' region-r columns] -> trailing K = 128 R of
-//   everything right of the super step (the next first region included) -> region(r0 + R),
-// then one persistent backward substitution (run_pbwd).  Every launch of a given slot holds the
-// same kind of work for all blocks, each at its OWN local step (work items carry it): blocks are
-// left-aligned (all start at launch 0; right alignment -- a block with fewer super steps starting
-// later -- measured no gain at configs 3-5).  Each work item is two int32:
-// [block / tile, (local step << 8) | pending panels or K multiple].
-static void build_tiled(const std::vector<int32_t>& mv, const std::vector<int32_t>& tb0, int copies,
-                        int nb, std::vector<TLaunch>& tl, std::vector<int32_t>& tlist) {
-    struct Blk { int32_t bq; int T64, Tz64, T2, Tz2, nr, R, S, off; };
-    int Rmax = 1;
-    const int run2 = chol::kRun2;
-    std::vector<Blk> bl;
-    int G = 0, Kmax = 0;
-    for (int c = 0; c < copies; ++c)
-        for (int32_t b : tb0) {
-            Blk k;
-            k.bq = b + c * nb;
-            k.T64 = (mv[b] + chol::kBT - 1) / chol::kBT;
-            k.Tz64 = mv[b] / chol::kBT;
-            k.T2 = (mv[b] + 127) / 128;
-            k.Tz2 = mv[b] / 128;
-            k.nr = (k.T64 + 1) / 2;
-            k.R = mv[b] >= kWideMin ? kWideSuper : kSuper;
-            Rmax = std::max(Rmax, k.R);
-            k.S = (k.nr + k.R - 1) / k.R;
-            G = std::max(G, k.S);
-            Kmax = std::max(Kmax, k.T64);
-            bl.push_back(k);
-        }
-    for (auto& k : bl) k.off = 0;   // left-aligned (right alignment measured: no gain at configs 3-5)
-    auto push_pairs = [&](int kind, const std::vector<int32_t>& v) {   // plain pair list
-        if (v.empty()) return;
-        TLaunch L{kind, 0, static_cast<int32_t>(tlist.size()), static_cast<int32_t>(v.size() / 2),
-                  static_cast<int32_t>(v.size() / 2)};
-        tlist.insert(tlist.end(), v.begin(), v.end());
-        tl.push_back(L);
-    };
-    auto region_launch = [&](const std::vector<int32_t>& v) { push_pairs(4, v); };
-    auto panel_launch = [&](const std::vector<int32_t>& v) { push_pairs(1, v); };
-    auto sync = [&](int kind, int ev, int strm) {
-        TLaunch L{kind, ev, 0, 0, 0};
-        L.strm = strm;
-        tl.push_back(L);
-    };
-    auto trailing_launch = [&](std::vector<std::vector<int32_t>>& q, int run, int strm) {
-        TLaunch L{5, 0, static_cast<int32_t>(tlist.size()), run, 0};
-        L.strm = strm;
-        size_t qmax = 0;
-        for (const auto& v : q) qmax = std::max(qmax, v.size() / 2);
-        // work item e (pair) runs on XCD e % 8
-        for (size_t i = 0; i < qmax; ++i)
-            for (int x = 0; x < kXcd; ++x) {
-                if (2 * i < q[x].size()) {
-                    tlist.push_back(q[x][2 * i]);
-                    tlist.push_back(q[x][2 * i + 1]);
-                } else {
-                    tlist.push_back(-1);
-                    tlist.push_back(0);
-                }
-            }
-        L.items = static_cast<int32_t>((tlist.size() - L.off) / 2);
-        if (L.items > 0) tl.push_back(L);
-    };
-    {   // region 0 of the blocks that start at super step 0
-        std::vector<int32_t> v;
-        for (const auto& k : bl)
-            if (k.off == 0) { v.push_back(k.bq); v.push_back(0); }
-        region_launch(v);
-    }
-    for (int g = 0; g < G; ++g) {
-        auto active = [&](const Blk& k) { return g >= k.off && g - k.off < k.S; };
-        std::vector<int32_t> v;
-        for (const auto& k : bl)      // panel(r0)
-            if (active(k)) {
-                const int r0 = (g - k.off) * k.R;
-                for (int i = 2 * r0 + 2; i <= k.Tz64; ++i) { v.push_back((k.bq << 16) | i); v.push_back(r0 << 8); }
-            }
-        panel_launch(v);
-        for (int j = 1; j < Rmax; ++j) {
-            std::vector<int32_t> rv, pv;
-            for (const auto& k : bl)
-                if (active(k) && j < k.R) {
-                    const int r = (g - k.off) * k.R + j;
-                    if (r >= k.nr) continue;
-                    rv.push_back(k.bq);
-                    rv.push_back((r << 8) | j);
-                    for (int i = 2 * r + 2; i <= k.Tz64; ++i) { pv.push_back((k.bq << 16) | i); pv.push_back((r << 8) | j); }
-                }
-            region_launch(rv);
-            panel_launch(pv);
-        }
-        // trailing: 128 x 128 tiles (I, J) right of the super step, rl + jlo <= J <= rl + jhi (near:
-        // the block's next R columns, far: the rest), LPT over per-XCD queues by tile row
-        auto trailing = [&](bool near, int strm, int run_force) {
-            std::vector<std::vector<int32_t>> q(kXcd);
-            std::vector<int64_t> load(kXcd, 0);
-            int64_t ntiles = 0;
-            for (const auto& k : bl)
-                if (active(k)) {
-                    const int r0 = (g - k.off) * k.R, rl = std::min(r0 + k.R, k.nr) - 1;
-                    if (rl + 1 >= k.nr) continue;
-                    const int jlo = near ? 1 : k.R + 1, jhi = near ? k.R : 1 << 20;
-                    for (int I = rl + jlo; I <= k.Tz2; ++I) {
-                        const int jm = std::min(std::min(I, k.T2 - 1), rl + jhi);
-                        if (jm >= rl + jlo) ntiles += jm - (rl + jlo) + 1;
-                    }
-                }
-            const int run = run_force ? run_force : (ntiles >= 1024 ? run2 : 1);
-            // 2-D placement: the tiles are cut into squares of kTrailSq x kTrailSq (tile rows I x tile
-            // columns J), a square's tiles go to one XCD, squares LPT over the XCDs.  The ~32 CUs of
-            // an XCD then work on one or two squares at a time, which read kTrailSq row panels and
-            // kTrailSq column panels between them through that XCD's L2 (keyed on the tile row
-            // alone, every XCD read every column panel from HBM)
-            // (smaller squares when a launch has few tiles, so the LPT over the XCDs stays balanced)
-            const int sq_w = ntiles >= 16 * kTrailSq * kTrailSq ? kTrailSq : ntiles >= 512 ? kTrailSq / 2 : 2;
-            struct Sq { int32_t bq, meta; int i0, i1, j0, j1, jhi; int64_t n; };
-            std::vector<Sq> sqs;
-            for (const auto& k : bl)
-                if (active(k)) {
-                    const int r0 = (g - k.off) * k.R, rl = std::min(r0 + k.R, k.nr) - 1;
-                    if (rl + 1 >= k.nr) continue;
-                    const int jlo = near ? 1 : k.R + 1, jhi = near ? k.R : 1 << 20;
-                    const int meta = (r0 << 8) | (rl - r0 + 1);
-                    const int jcap = std::min(k.T2 - 1, rl + jhi);
-                    for (int i0 = rl + jlo; i0 <= k.Tz2; i0 += sq_w)
-                        for (int j0 = rl + jlo; j0 <= std::min(i0 + sq_w - 1, jcap); j0 += sq_w) {
-                            const int i1 = std::min(i0 + sq_w - 1, k.Tz2), j1 = std::min(j0 + sq_w - 1, jcap);
-                            int64_t n = 0;
-                            for (int I = i0; I <= i1; ++I) n += std::max(0, std::min(I, j1) - j0 + 1);
-                            if (n > 0) sqs.push_back(Sq{k.bq, meta, i0, i1, j0, j1, jcap, n});
-                        }
-                }
-            std::stable_sort(sqs.begin(), sqs.end(), [](const Sq& a, const Sq& b) { return a.n > b.n; });
-            for (const Sq& sq : sqs) {
-                const int x = static_cast<int>(std::min_element(load.begin(), load.end()) - load.begin());
-                for (int I = sq.i0; I <= sq.i1; ++I) {
-                    const int jm = std::min(I, sq.j1);
-                    for (int J = sq.j0; J <= jm; J += run) {
-                        q[x].push_back((sq.bq << 16) | (I << 8) | J);
-                        q[x].push_back(sq.meta);
-                    }
-                }
-                load[x] += sq.n;
-            }
-            trailing_launch(q, run, strm);
-        };
-        // lookahead: the next super step's R tile columns ("near": chain stream, one tile per
-        // work item) are updated first; the rest ("far": stream 1) overlaps the next super step's
-        // regions and panels.  Tiles of near(g) were far(g-1)'s.
-        sync(kTlRecord, 2 * g, 0);
-        if (g > 0) sync(kTlWait, 2 * g - 1, 0);
-        trailing(true, 0, 1);
-        sync(kTlWait, 2 * g, 1);
-        trailing(false, 1, 0);
-        sync(kTlRecord, 2 * g + 1, 1);
-        {   // next super step's first region; region 0 of the blocks that start at g + 1
-            std::vector<int32_t> v;
-            for (const auto& k : bl) {
-                if (active(k)) {
-                    const int r0 = (g - k.off) * k.R, rn = r0 + k.R;
-                    if (rn < k.nr) { v.push_back(k.bq); v.push_back(rn << 8); }
-                } else if (k.off == g + 1) {
-                    v.push_back(k.bq);
-                    v.push_back(0);
-                }
-            }
-            region_launch(v);
-        }
-    }
-    if (G > 0) sync(kTlWait, 2 * G - 1, 0);   // the last far update
-    // (the backward substitution is one persistent launch after the sequence: run_pbwd)
-}
-
 template <int NR>
 static hipError_t set_trsv_lds() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dbslmm_trsv_fwd<NR>),
@@ -1064,32 +837,24 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
               "n_ref must be at most 1,863,936 (exact FP4 Gram accumulation)");
     ARG_CHECK(ctx, pr->s_ptr && (pr->s_ptr[pr->num_block] == 0 || (pr->s_pos && pr->z_s)), "bad small CSR");
     ARG_CHECK(ctx, pr->sigma_s > 0.0 && std::isfinite(pr->sigma_s), "sigma_s must be > 0");
-    const int64_t bps = pr->n_ref / 4 + (pr->n_ref % 4 ? 1 : 0);
-    const int64_t n_snp_bed = (pr->bed_len - 3) / bps;
-    ARG_CHECK(ctx, pr->bed_len >= 3 + bps, "bed image shorter than one SNP row");
+    ARG_CHECK(ctx, pr->bed_len >= 3 + bed_row_bytes(pr->n_ref), "bed image shorter than one SNP row");
     KEY_CHECK(ctx, pr->bed, pr->bed_len, pr->n_ref);
     const bool has_l = pr->l_ptr != nullptr;
     if (has_l) ARG_CHECK(ctx, pr->l_ptr[pr->num_block] == 0 || (pr->l_pos && pr->z_l), "bad large CSR");
+    const dbslmm_options op = pr->opts ? *pr->opts : dbslmm_options{};
+    // ---- host-side layout (plan_layout.hpp); its upload-only lists go with L
+    PlanLayout L;
+    if (const int rc = build_plan_layout(*pr, op, ctx->n_cu, L, ctx->err)) return rc;
 
     auto* p = new dbslmm_plan();
+    static_cast<PlanLayout::Kept&>(*p) = std::move(L.keep);
     p->ctx = ctx;
     p->n_ref = pr->n_ref;
     p->n_obs = pr->n_obs;
     p->num_block = pr->num_block;
     p->sigma_s = pr->sigma_s;
     p->tau = pr->tau;
-    p->kpad = round_up(pr->n_ref, gram::kKpadAlign);   // the FP4 Gram's K stage (gram_big: 128 divides it)
     p->bed_len = pr->bed_len;
-    const dbslmm_options op = pr->opts ? *pr->opts : dbslmm_options{};
-    ARG_CHECK(ctx, op.tiled_min >= 0 && op.gram_big_min >= 0 && op.gram_huge_min >= 0 &&
-                   (op.h2f_mode == 0 || op.h2f_mode == 1) && op.cheb_tol >= 0.0 &&
-                   (op.large_cheb == 0 || op.large_cheb == -1) && (op.cheb_fused == 0 || op.cheb_fused == 1) &&
-                   op.debug_delay_us >= -100000 && op.debug_delay_us <= 100000 &&
-                   (op.debug_stop == 0 || op.debug_stop == 1) && op.sub_split >= -1 && op.sub_split <= 2 &&
-                   op.sub_grid_lead >= 0 && op.sub_grid_rest >= 0 && op.shard_copies >= 0 &&
-                   op.shard_copies <= 64 && op.h2f_iter >= 0 && op.h2f_iter <= 2 && op.solver >= 0 &&
-                   op.solver <= 2 && op.pcg_tol >= 0.0 && op.pcg_maxit >= 0 && op.stream_out >= -1 &&
-                   op.stream_out <= 1 && op.pcg_block_wgs >= 0, "bad dbslmm_options");
     p->solver = op.solver;
     p->pcg_fused = op.pcg_whole >= 0;
     p->stream_out = op.stream_out >= 0;
@@ -1103,339 +868,6 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     p->debug_delay_us = op.debug_delay_us;
     p->debug_stop = op.debug_stop;
     if (op.cheb_tol > 0.0) p->cheb_tol = std::max(1e-16, op.cheb_tol);
-    p->n_s = pr->s_ptr[pr->num_block];
-    p->n_l = has_l ? pr->l_ptr[pr->num_block] : 0;
-
-    // ---- host-side layout
-    std::vector<int32_t> slot_pos, slot_block, slot_out, row0, mv, msv, ldv, blk_id;
-    std::vector<double> z;
-    std::vector<int64_t> matoff;
-    std::vector<GramTile> tiles;
-    const int64_t gram_big_min = op.gram_big_min > 0 ? op.gram_big_min : kGramBigMinDefault;
-    // the 256-tile kernel pays once its K loop outweighs its 512 KB fp64 epilogue per tile
-    const int64_t gram_huge_min = op.gram_huge_min > 0 ? op.gram_huge_min
-                                  : p->kpad >= 4096 ? kGramHugeMinDefault : 2 * kGramHugeMinDefault;
-    std::vector<std::vector<GramTile>> xq(kXcd), hq(kXcd), lq(kXcd), nq(kXcd);
-    std::vector<double> xload(kXcd, 0.0), hload(kXcd, 0.0), lload(kXcd, 0.0), nload(kXcd, 0.0);
-    int64_t moff = 0;
-    double ops_alg = 0, ops_exec = 0, chol_flops_large = 0, chol_flops_small = 0, chol_flops_tiled = 0;
-    int64_t tiled_min = kTiledMinDefault;
-    if (op.tiled_min > 0) {
-        tiled_min = std::max<int64_t>(64, op.tiled_min);
-    } else {
-        // no block reaches the default: the single-workgroup solve of the largest blocks is then
-        // the critical path itself, and spreading the blocks of >= kTiledMinSmall SNPs over many
-        // workgroups shortens it (config 2: 0.66 -> 0.55 ms/step); with bigger blocks the tiled
-        // sequence is the critical path and the mid-size blocks stay in its shadow
-        int64_t mmax = 0;
-        for (int b = 0; b < pr->num_block; ++b)
-            mmax = std::max<int64_t>(mmax, pr->s_ptr[b + 1] - pr->s_ptr[b] +
-                                               (has_l ? pr->l_ptr[b + 1] - pr->l_ptr[b] : 0));
-        if (mmax < 512) tiled_min = kTiledMinSmall;
-    }
-    p->tiled_min = static_cast<int32_t>(std::min<int64_t>(tiled_min, INT32_MAX));
-    // lead group: the tiled blocks with the longest factorisation chains (m >= lead_min); their
-    // Gram tiles form the first 256-tile launch and their sequence starts right after it
-    int64_t lead_min = INT64_MAX;
-    {
-        int64_t mmax = 0, n_lead = 0, n_rest = 0;
-        for (int b = 0; b < pr->num_block; ++b)
-            mmax = std::max<int64_t>(mmax, pr->s_ptr[b + 1] - pr->s_ptr[b] +
-                                               (has_l ? pr->l_ptr[b + 1] - pr->l_ptr[b] : 0));
-        if (op.lead_min >= 0) {
-            // (round 4, config 4 same box, with the substitution grids below: lead >= 1536 on
-            // 80 / 176 workgroups 42.02 / 42.11 ms against 42.85-42.97 for max(2048, m_max / 2) on
-            // 64 / 192; 1280 42.47, 1792 42.44, 1536 on 64 / 192 43.10, on 72 / 184 42.35,
-            // on 96 / 160 43.29 -- profiles/r04/ab/lead_grids.txt)
-            lead_min = op.lead_min > 0 ? op.lead_min : std::max<int64_t>(kLeadMinDefault, mmax / 8);
-            lead_min = std::max({lead_min, tiled_min, gram_huge_min});
-            for (int b = 0; b < pr->num_block; ++b) {
-                const int64_t m = pr->s_ptr[b + 1] - pr->s_ptr[b] + (has_l ? pr->l_ptr[b + 1] - pr->l_ptr[b] : 0);
-                if (m >= lead_min) ++n_lead;
-                else if (m >= tiled_min) ++n_rest;
-            }
-            if (n_lead == 0 || n_rest == 0) lead_min = INT64_MAX;   // nothing to overlap
-        }
-    }
-    std::vector<char> is_tiled;
-    for (int b = 0; b < pr->num_block; ++b) {
-        const int64_t s0 = pr->s_ptr[b], ms = pr->s_ptr[b + 1] - s0;
-        const int64_t l0 = has_l ? pr->l_ptr[b] : 0, ml = has_l ? pr->l_ptr[b + 1] - l0 : 0;
-        if (ms < 0 || ml < 0) { ctx->err = "CSR offsets not monotone"; dbslmm_plan_destroy(p); return DBSLMM_E_ARG; }
-        const int64_t m = ms + ml;
-        if (m == 0) { p->h_empty.push_back(b); continue; }
-        const int nb = static_cast<int>(row0.size());
-        const bool tiled = m >= tiled_min;
-        // packed work items: 128-row tile / region indices in 8 bits, block (x copies) in 15
-        if (tiled && (m >= kTiledMaxM || nb >= 32767)) {
-            ctx->err = "LD block too large for the tiled path (m must be < 32640 SNPs)";
-            dbslmm_plan_destroy(p);
-            return DBSLMM_E_ARG;
-        }
-        is_tiled.push_back(tiled);
-        // + the z row of the bordered matrix; the tiled path works on 128 x 128 regions
-        const int64_t ld = round_up(m + 1, tiled ? 2 * chol::kBT : kTile);
-        row0.push_back(static_cast<int32_t>(slot_pos.size()));
-        mv.push_back(static_cast<int32_t>(m));
-        msv.push_back(static_cast<int32_t>(ms));
-        ldv.push_back(static_cast<int32_t>(ld));
-        blk_id.push_back(b);
-        matoff.push_back(moff);
-        moff += ld * ld;
-        for (int64_t i = 0; i < ms; ++i) {
-            const int32_t r = pr->s_pos[s0 + i];
-            if (r < 0 || r >= n_snp_bed) { ctx->err = "small SNP bed row out of range"; dbslmm_plan_destroy(p); return DBSLMM_E_ARG; }
-            slot_pos.push_back(r);
-            slot_block.push_back(nb);
-            slot_out.push_back(static_cast<int32_t>(s0 + i));
-            z.push_back(pr->z_s[s0 + i]);
-        }
-        for (int64_t i = 0; i < ml; ++i) {
-            const int32_t r = pr->l_pos[l0 + i];
-            if (r < 0 || r >= n_snp_bed) { ctx->err = "large SNP bed row out of range"; dbslmm_plan_destroy(p); return DBSLMM_E_ARG; }
-            slot_pos.push_back(r);
-            slot_block.push_back(nb);
-            slot_out.push_back(static_cast<int32_t>(-1 - (l0 + i)));
-            z.push_back(pr->z_l[l0 + i]);
-        }
-        for (int64_t i = m; i < ld; ++i) {
-            slot_pos.push_back(-1);
-            slot_block.push_back(nb);
-            slot_out.push_back(INT32_MIN);
-            z.push_back(0.0);
-        }
-        if (m >= gram_huge_min) {   // 256 x 256 tiles
-            const int T = static_cast<int>((m + gram::kHT - 1) / gram::kHT);
-            auto& q = m >= lead_min ? lq : tiled ? hq : nq;
-            auto& ld_ = m >= lead_min ? lload : tiled ? hload : nload;
-            // squares of kGramSq x kGramSq tiles (lower triangle), each on the least-loaded XCD:
-            // the workgroups in flight on an XCD share kGramSq row panels of each operand
-            for (int si = 0; si < T; si += kGramSq)
-                for (int sj = 0; sj <= si; sj += kGramSq) {
-                    const int x = static_cast<int>(std::min_element(ld_.begin(), ld_.end()) - ld_.begin());
-                    for (int ti = si; ti < std::min(T, si + kGramSq); ++ti)
-                        for (int tj = sj; tj < std::min(ti + 1, sj + kGramSq); ++tj) {
-                            q[x].push_back({nb, ti, tj, 0});
-                            ld_[x] += 1;
-                        }
-                }
-            // MFMA work actually issued (dbslmm_gram_huge): 32 x 32 sub-tiles with rows and
-            // columns < m, and on a diagonal tile not strictly above its diagonal
-            int64_t sub = 0;
-            for (int ti = 0; ti < T; ++ti)
-                for (int tj = 0; tj <= ti; ++tj) {
-                    const int64_t rv = std::min<int64_t>(gram::kHT, m - int64_t(gram::kHT) * ti);
-                    const int64_t cv = std::min<int64_t>(gram::kHT, m - int64_t(gram::kHT) * tj);
-                    const int64_t ni = (rv + 31) / 32, nj = (cv + 31) / 32;
-                    sub += ti != tj ? ni * nj : ni * (ni + 1) / 2;   // (diagonal: rv == cv)
-                }
-            ops_exec += 2.0 * p->kpad * 32 * 32 * sub;
-        } else if (m >= gram_big_min) {   // 128 x 128 tiles, the block's queue on the least-loaded XCD
-            const int T = static_cast<int>((m + gram::kGT - 1) / gram::kGT);
-            const int x = static_cast<int>(std::min_element(xload.begin(), xload.end()) - xload.begin());
-            for (int ti = 0; ti < T; ++ti)
-                for (int tj = 0; tj <= ti; ++tj) xq[x].push_back({nb, ti, tj, 0});
-            xload[x] += T * (T + 1) / 2;
-            // (dbslmm_gram_big: whole 128 x 128 tiles; a diagonal tile skips its upper quadrant)
-            ops_exec += 2.0 * p->kpad * gram::kGT * gram::kGT * (T * (T - 1) / 2 + 0.75 * T);
-        } else {
-            const int T = static_cast<int>((m + kTile - 1) / kTile);   // tiles holding SNP rows
-            for (int ti = 0; ti < T; ++ti)
-                for (int tj = 0; tj <= ti; ++tj) tiles.push_back({nb, ti, tj, 0});
-            ops_exec += 2.0 * p->kpad * kTile * kTile * (T * (T + 1) / 2);
-        }
-        ops_alg += static_cast<double>(pr->n_ref) * m * (m + 1);
-        (tiled ? chol_flops_tiled : ld > chol::kSmallLd ? chol_flops_large : chol_flops_small) +=
-            m * static_cast<double>(m) * m / 3.0 + 2.0 * m * m;
-    }
-    p->n_nonempty = static_cast<int32_t>(row0.size());
-    p->n_slots = static_cast<int32_t>(slot_pos.size());
-    p->h_ms = msv;
-    p->h_row0 = row0;
-    for (size_t b = 0; b < mv.size(); ++b) p->has_large = p->has_large || mv[b] > msv[b];
-    p->h_slot_out = slot_out;
-    p->n_tiles = static_cast<int32_t>(tiles.size());
-    std::vector<GramTile> btiles;
-    {
-        size_t qmax = 0;
-        for (const auto& q : xq) qmax = std::max(qmax, q.size());
-        btiles.assign(qmax * kXcd, GramTile{-1, 0, 0, 0});
-        for (int x = 0; x < kXcd; ++x)
-            for (size_t i = 0; i < xq[x].size(); ++i) btiles[i * kXcd + x] = xq[x][i];
-        p->n_btiles = static_cast<int32_t>(btiles.size());
-    }
-    // [lead group's queues | the other tiled blocks' | the non-tiled blocks'], entry e on XCD e % 8
-    std::vector<GramTile> htiles;
-    for (const auto* qs : {&lq, &hq, &nq}) {
-        size_t qmax = 0;
-        for (const auto& q : *qs) qmax = std::max(qmax, q.size());
-        const size_t base = htiles.size();
-        htiles.resize(base + qmax * kXcd, GramTile{-1, 0, 0, 0});
-        for (int x = 0; x < kXcd; ++x)
-            for (size_t i = 0; i < (*qs)[x].size(); ++i) htiles[base + i * kXcd + x] = (*qs)[x][i];
-        if (qs == &lq) p->n_htiles_lead = static_cast<int32_t>(htiles.size());
-        if (qs == &hq) p->n_htiles_tiled = static_cast<int32_t>(htiles.size());
-    }
-    {
-        // (without tiled blocks stream2 runs chol_small, which needs the whole Gram)
-        bool all_huge = true, any_tiled = false;
-        for (size_t b = 0; b < mv.size(); ++b) {
-            any_tiled = any_tiled || is_tiled[b];
-            if (is_tiled[b] && mv[b] < gram_huge_min) all_huge = false;
-        }
-        // (lead_min < 0: no overlap of the Gram and the factorisation at all)
-        p->early_fork = all_huge && any_tiled && op.lead_min >= 0;
-    }
-    p->n_htiles = static_cast<int32_t>(htiles.size());
-    p->M_elems = moff;
-    p->h_ld = ldv;
-    p->h_blk_id = blk_id;
-    p->h_matoff = matoff;
-    (void)build_out_ranges(pr->num_block, pr->s_ptr, has_l ? pr->l_ptr : nullptr, p->h_orange);   // (offsets checked above)
-    // Cholesky work lists: large blocks (ld > 64, one workgroup each) then small blocks (one
-    // wave each), each largest first (longest-processing-time order)
-    std::vector<int32_t> order(p->n_nonempty);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return mv[a] > mv[c]; });
-    order.erase(std::remove_if(order.begin(), order.end(), [&](int b) { return is_tiled[b] != 0; }),
-                order.end());
-    int32_t large_ld_max = 0;
-    for (int32_t b : order) {
-        (ldv[b] > chol::kSmallLd ? p->n_large : p->n_small)++;
-        if (ldv[b] > chol::kSmallLd) large_ld_max = std::max(large_ld_max, ldv[b]);
-    }
-    // dbslmm_chol_cheb holds a block's vectors in LDS for ld <= kChebMaxM (the default tiled_min
-    // guarantees it; a larger tiled_min leaves bigger blocks on chol_large, whose h2f copies are
-    // then all factored)
-    p->large_cheb_ok = op.large_cheb == 0 && large_ld_max <= chol::kChebMaxM;
-    std::vector<int32_t> tlist;
-    {
-        std::vector<int32_t> tb, tb_lead, tb_rest;
-        for (int b = 0; b < p->n_nonempty; ++b)
-            if (is_tiled[b]) {
-                tb.push_back(b);
-                (mv[b] >= lead_min ? tb_lead : tb_rest).push_back(b);
-            }
-        p->n_tiled = static_cast<int32_t>(tb.size());
-        p->h_m = mv;
-        p->h_tb = tb;
-        if (tb_lead.empty()) {
-            build_tiled(mv, tb, 1, p->n_nonempty, p->tl, tlist);
-        } else {
-            build_tiled(mv, tb_lead, 1, p->n_nonempty, p->tl, tlist);
-            build_tiled(mv, tb_rest, 1, p->n_nonempty, p->tl_rest, tlist);
-        }
-    }
-    // substitution work lists (trsv.hip): 64-row tiles of the tiled blocks; forward in order of
-    // (tile, block), backward in order of (tiles from the end, block) -- every dependency of an
-    // item comes earlier in its list
-    std::vector<int32_t> tri_f, tri_b, foff(std::max(1, p->n_nonempty), 0), tcheb_list;
-    {
-        int32_t nf = 0, tmax = 0;
-        for (int32_t b : p->h_tb) {
-            foff[b] = nf;
-            const int T = (mv[b] + trsv::kT - 1) / trsv::kT;
-            nf += T;
-            tmax = std::max(tmax, T);
-        }
-        p->n_tflags = nf;
-        (void)tmax;
-        // ticket order: tile position relative to the block's length minus alpha T / Tmax (bigger
-        // blocks' tiles are claimed earlier: their chains are longer; ties: longer block first),
-        // monotone in the position within each block, so every dependency comes earlier.  Split
-        // substitutions (sub_split): the lead group's items first, then the rest group's, each
-        // group in that order (and d_tb = [lead blocks | rest blocks])
-        // (config 4, same box: one sequence 45.1-45.5 ms per step; split on 64 / 192 workgroups
-        // 43.9-44.1; 96 / 160 44.9; 128 / 128 47.1; a rest grid of every CU 51-56 -- its
-        // persistent workgroups then hold the CUs the lead factorisation's tail still needs)
-        // (cheb_fused = 1 runs every Chebyshev pass of ALL tiled items in one launch: no groups)
-        p->sub_split = op.sub_split >= 0 && !p->tl_rest.empty() && !p->cheb_fused;
-        // lead workgroups by the lead group's share f of the factor bytes a pass streams:
-        // 2.05 f^1.5 of the CUs, within [1/16, 1/2]: config 4's f = 0.285 gives the 80 of 256 tuned
-        // there in round 4; a shard whose lead group is small (the bulk device of the 8-GPU plan,
-        // f = 0.135: 26) gives its rest group the CUs instead of leaving 5/16 of the chip to a few
-        // short chains (that device 19.4 ms at 80 lead workgroups, 17.1 at 24 / 32, 18.3 at 16)
-        {
-            double lb = 0.0, ab = 0.0;
-            for (int32_t b : p->h_tb) {
-                const double T = (mv[b] + trsv::kT - 1) / trsv::kT, by = T * (T + 1) / 2;
-                ab += by;
-                if (mv[b] >= lead_min) lb += by;
-            }
-            const double share = ab > 0 ? lb / ab : 0.0;
-            const int g = static_cast<int>(std::lround(ctx->n_cu * 2.05 * share * std::sqrt(share)));
-            p->sub_grid_lead = op.sub_grid_lead > 0 ? op.sub_grid_lead
-                                                    : std::clamp(g, std::max(1, ctx->n_cu / 16), std::max(1, ctx->n_cu / 2));
-        }
-        p->sub_grid_rest = op.sub_grid_rest > 0 ? op.sub_grid_rest : std::max(1, ctx->n_cu - p->sub_grid_lead);
-        auto grp_of = [&](int32_t b) { return p->sub_split && mv[b] < lead_min ? 1 : 0; };
-        struct It { int grp; double key; int T; int32_t b, I; };
-        std::vector<It> v;
-        constexpr double alpha = 0.25;
-        int tmx = 1;
-        for (int32_t b : p->h_tb) tmx = std::max(tmx, (mv[b] + trsv::kT - 1) / trsv::kT);
-        for (int32_t b : p->h_tb) {
-            const int T = (mv[b] + trsv::kT - 1) / trsv::kT;
-            for (int I = 0; I < T; ++I) v.push_back({grp_of(b), static_cast<double>(I) / T - alpha * T / tmx, T, b, I});
-        }
-        std::stable_sort(v.begin(), v.end(), [&](const It& x, const It& y) {
-            return x.grp != y.grp ? x.grp < y.grp : x.key != y.key ? x.key < y.key : x.T > y.T;
-        });
-        p->n_titems_lead = static_cast<int32_t>(std::count_if(v.begin(), v.end(), [](const It& x) { return x.grp == 0; }));
-        if (p->sub_split) {
-            std::stable_partition(p->h_tb.begin(), p->h_tb.end(), [&](int32_t b) { return grp_of(b) == 0; });
-            p->n_tb_lead = static_cast<int32_t>(std::count_if(p->h_tb.begin(), p->h_tb.end(),
-                                                              [&](int32_t b) { return grp_of(b) == 0; }));
-        }
-        // whole-block Chebyshev passes for the rest group (sub_split = 2): every rest block within
-        // kTChebMaxM (the work vector of NR copies in LDS; one workgroup streams the block alone)
-        if (p->sub_split && op.sub_split == 2) {
-            std::vector<int32_t> rb(p->h_tb.begin() + p->n_tb_lead, p->h_tb.end());
-            int32_t tmax_r = 0;
-            for (int32_t b : rb) tmax_r = std::max(tmax_r, (mv[b] + trsv::kT - 1) / trsv::kT);
-            if (!rb.empty() && tmax_r * trsv::kT <= kTChebMaxM) {
-                std::stable_sort(rb.begin(), rb.end(), [&](int32_t x, int32_t y) { return mv[x] > mv[y]; });
-                tcheb_list = rb;
-                p->sub_block = true;
-                p->n_tcheb = static_cast<int32_t>(rb.size());
-                p->tcheb_vld = tmax_r * trsv::kT;
-            }
-        }
-        for (const It& x : v) {
-            tri_f.push_back(x.b);
-            tri_f.push_back(x.I);
-            tri_b.push_back(x.b);
-            tri_b.push_back(x.T - 1 - x.I);   // backward: the same order from the other end
-        }
-        p->n_titems = static_cast<int32_t>(tri_f.size() / 2);
-        double tb = 0.0;   // factor bytes one substitution launch reads: T (T + 1) / 2 tiles per block
-        for (int32_t b : p->h_tb) {
-            const double T = (mv[b] + trsv::kT - 1) / trsv::kT;
-            tb += T * (T + 1) / 2 * trsv::kT * trsv::kT * sizeof(double);
-        }
-        p->wl[13] = tb;
-    }
-    const double n_snp = static_cast<double>(p->n_s + p->n_l);
-    p->wl[0] = n_snp;
-    // bytes the statistics gather reads per slot: its image row, the row's table entry, its block
-    p->wl[1] = static_cast<double>(p->n_slots) * (sizeof(int32_t) + sizeof(v4i) + sizeof(int32_t));
-    // bytes it writes: S, mu, 1/sd per slot and the blocks' missing-call flags
-    p->wl[2] = static_cast<double>(p->n_slots) * 3 * sizeof(double) + static_cast<double>(p->n_nonempty) * sizeof(int32_t);
-    p->wl[3] = ops_alg;
-    p->wl[4] = ops_exec;
-    p->wl[5] = chol_flops_large;
-    p->wl[6] = p->n_nonempty;
-    p->wl[7] = p->n_tiles + p->n_btiles + p->n_htiles;
-    p->wl[8] = chol_flops_small;
-    p->wl[9] = p->n_large;
-    p->wl[10] = chol_flops_tiled;
-    p->wl[11] = p->n_tiled;
-    p->wl[12] = static_cast<double>(std::count_if(p->tl.begin(), p->tl.end(),
-                                                  [](const TLaunch& L) { return L.kind < kTlRecord; }) +
-                                    std::count_if(p->tl_rest.begin(), p->tl_rest.end(),
-                                                  [](const TLaunch& L) { return L.kind < kTlRecord; }));
-    p->wl[14] = 0;
-    p->wl[15] = -1;
 
     // ---- device allocations
     hipError_t e = hipSetDevice(ctx->device);
@@ -1451,26 +883,26 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     // (every memset of the plan's buffers is ordered on the main stream, which every run starts
     // on: a null-stream hipMemset is not ordered against the context's non-blocking streams, and
     // one still running under the first run's Gram would zero matrix entries behind it)
-    if ((e = dev_upload(&p->d_slot_pos, slot_pos, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_slot_block, slot_block, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_slot_out, slot_out, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_z, z, ctx->stream)) != hipSuccess) return fail("upload z");
-    if ((e = dev_upload(&p->d_row0, row0, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_m, mv, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_ms, msv, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_ld, ldv, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_matoff, matoff, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_blk_id, blk_id, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_order, order, ctx->stream)) != hipSuccess) return fail("upload order");
-    if ((e = dev_upload(&p->d_tiles, tiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_btiles, btiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_htiles, htiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_tlist, tlist, ctx->stream)) != hipSuccess) return fail("upload tiled lists");
-    if ((e = dev_upload(&p->d_tri_f, tri_f, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if ((e = dev_upload(&p->d_tri_b, tri_b, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if ((e = dev_upload(&p->d_foff, foff, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = dev_upload(&p->d_slot_pos, L.slot_pos, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = dev_upload(&p->d_slot_block, L.slot_block, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = dev_upload(&p->d_slot_out, p->h_slot_out, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = dev_upload(&p->d_z, L.z, ctx->stream)) != hipSuccess) return fail("upload z");
+    if ((e = dev_upload(&p->d_row0, p->h_row0, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_m, p->h_m, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_ms, p->h_ms, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_ld, p->h_ld, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_matoff, p->h_matoff, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_blk_id, p->h_blk_id, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = dev_upload(&p->d_order, L.order, ctx->stream)) != hipSuccess) return fail("upload order");
+    if ((e = dev_upload(&p->d_tiles, L.tiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = dev_upload(&p->d_btiles, L.btiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = dev_upload(&p->d_htiles, L.htiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = dev_upload(&p->d_tlist, L.tlist, ctx->stream)) != hipSuccess) return fail("upload tiled lists");
+    if ((e = dev_upload(&p->d_tri_f, L.tri_f, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = dev_upload(&p->d_tri_b, L.tri_b, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = dev_upload(&p->d_foff, L.foff, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
     if ((e = dev_upload(&p->d_tb, p->h_tb, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if (!tcheb_list.empty() && (e = dev_upload(&p->d_tcheb_blocks, tcheb_list, ctx->stream)) != hipSuccess)
+    if (!L.tcheb_list.empty() && (e = dev_upload(&p->d_tcheb_blocks, L.tcheb_list, ctx->stream)) != hipSuccess)
         return fail("upload trsv lists");
     // [tile flags | ticket counter | error word | spare]
     if ((e = hipMalloc(&p->d_tflags, (p->n_tflags + 3) * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc trsv flags");
@@ -1515,30 +947,33 @@ int dbslmm_plan_enable_timing(dbslmm_plan* p, int enable) {
 static int collect_timing(dbslmm_plan* p) {
     dbslmm_ctx* ctx = p->ctx;
     for (int r = 0; r < p->runs_pending; ++r) {
-        hipEvent_t* e = &p->ev[kEvPerRun * r];
+        hipEvent_t* e = &p->ev[kEvCount * r];
         // event times from the run's start; with split substitutions the tiled factorisation +
-        // backward of the two groups ends on two streams (8: lead, 11: rest) and the Chebyshev
-        // passes start there: tiled = 6 -> max(8, 11), trsv = min(8, 11) -> 7 (the spans overlap)
-        float t[kEvPerRun] = {0.f};
+        // backward of the two groups ends on two streams (kEvTiledEnd: lead, kEvRestEnd: rest) and
+        // the Chebyshev passes start there: tiled = kEvTiledBegin -> the later of the two, trsv =
+        // the earlier of the two -> kEvEnd (the spans overlap)
+        float t[kEvCount] = {0.f};
         if (r < static_cast<int>(p->run_route.size()) && p->run_route[r]) {
-            // PCG: statistics, Gram, iterations; the only instants this route records are 0, 1, 2, 3, 4, 7
-            for (int k : {1, 2, 3, 4, 7}) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[0], e[k]));
+            // PCG: statistics, Gram, iterations; the only instants this route records
+            for (Ev k : {kEvStatsEnd, kEvGramEnd, kEvPcgBlockBegin, kEvPcgBlockEnd, kEvEnd})
+                HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[kEvStart], e[k]));
             float span[DBSLMM_K_COUNT] = {0.f};
-            span[DBSLMM_K_UNPACK] = t[1];
-            span[DBSLMM_K_GRAM] = t[2] - t[1];
-            span[DBSLMM_K_PCG] = t[7] - t[2];
-            span[DBSLMM_K_PCG_BLOCK] = t[4] - t[3];   // (inside the PCG span, on the second stream)
+            span[DBSLMM_K_UNPACK] = t[kEvStatsEnd];
+            span[DBSLMM_K_GRAM] = t[kEvGramEnd] - t[kEvStatsEnd];
+            span[DBSLMM_K_PCG] = t[kEvEnd] - t[kEvGramEnd];
+            span[DBSLMM_K_PCG_BLOCK] = t[kEvPcgBlockEnd] - t[kEvPcgBlockBegin];   // (inside the PCG span, on the second stream)
             for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
             p->ms_runs++;
             continue;
         }
-        for (int k = 1; k < kEvPerRun; ++k) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[0], e[k]));
-        const float fend = std::max(t[8], t[11]), cstart = std::min(t[8], t[11]);
-        float span[DBSLMM_K_COUNT] = {t[1], t[2] - t[1], t[3] - t[2], t[5] - t[4], fend - t[6], t[7] - cstart, 0.f, 0.f};
+        for (int k = 1; k < kEvCount; ++k) HIP_TRY(ctx, hipEventElapsedTime(&t[k], e[kEvStart], e[k]));
+        const float fend = std::max(t[kEvTiledEnd], t[kEvRestEnd]), cstart = std::min(t[kEvTiledEnd], t[kEvRestEnd]);
+        float span[DBSLMM_K_COUNT] = {t[kEvStatsEnd], t[kEvGramEnd] - t[kEvStatsEnd], t[kEvLargeEnd] - t[kEvGramEnd],
+                                      t[kEvSmallEnd] - t[kEvSmallBegin], fend - t[kEvTiledBegin], t[kEvEnd] - cstart, 0.f, 0.f};
         for (int k = 0; k < DBSLMM_K_COUNT; ++k) p->ms_acc[k] += span[k];
-        // the lead group's Gram (9 -> 10) sits inside the statistics span (0 -> 1)
+        // the lead group's Gram sits inside the statistics span (kEvStart -> kEvStatsEnd)
         float lg = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&lg, e[9], e[10]));
+        HIP_TRY(ctx, hipEventElapsedTime(&lg, e[kEvLeadGramBegin], e[kEvLeadGramEnd]));
         p->ms_acc[0] -= lg;
         p->ms_acc[1] += lg;
         p->ms_runs++;
@@ -2436,55 +1871,95 @@ static int so_prepare(dbslmm_plan* p, int n) {
     return DBSLMM_OK;
 }
 
+// Open a timed run (dbslmm_plan_enable_timing): *ev = its kEvCount events, created on first use, and
+// its route noted for collect_timing.  An untimed run leaves *ev null.
+static int open_timed_run(dbslmm_plan* p, bool pcg, hipEvent_t** ev) {
+    *ev = nullptr;
+    if (!p->timing) return DBSLMM_OK;
+    const size_t need = kEvCount * static_cast<size_t>(p->runs_pending + 1);
+    while (p->ev.size() < need) {
+        hipEvent_t e;
+        HIP_TRY(p->ctx, hipEventCreate(&e));
+        p->ev.push_back(e);
+    }
+    *ev = &p->ev[kEvCount * p->runs_pending];
+    p->runs_pending++;
+    p->run_route.resize(p->runs_pending);
+    p->run_route.back() = pcg ? 1 : 0;
+    return DBSLMM_OK;
+}
+
+// Record the instants `ks` of a timed run on stream st, in that order: the phases a run does not
+// have, so that its event set is complete (collect_timing).  Nothing for an untimed run.
+static int record_instants(dbslmm_ctx* ctx, hipEvent_t* ev, std::initializer_list<Ev> ks, hipStream_t st) {
+    if (!ev) return DBSLMM_OK;
+    for (Ev k : ks) HIP_TRY(ctx, hipEventRecord(ev[k], st));
+    return DBSLMM_OK;
+}
+
+// What a Gram launch writes: copies [0, ncopy) of every block's matrix, except that blocks with
+// m >= tmin_copy write copy tcopy only (tcopy < 0: all); the PCG route also stores the integer
+// Gram as uint16 (g16 with its per-block offsets and strides; null on the factorisation route).
+struct GramOut {
+    int32_t ncopy, tmin_copy, tcopy;
+    uint16_t* g16;
+    const int64_t* off16;
+    const int32_t* ld16;
+};
+enum GramKernel { kGramI8, kGramBig, kGramHuge };
+// One Gram launch on stream st: the `nt` tiles at `tiles` by kernel `which` (nt = 0: nothing).
+static hipError_t launch_gram(const dbslmm_plan* p, hipStream_t st, GramKernel which, const GramTile* tiles,
+                              int32_t nt, const GramOut& o) {
+    if (nt <= 0) return hipSuccess;
+    struct Shape {
+        decltype(&dbslmm_gram_i8) kernel;
+        int tiles_per_wg, threads;
+        size_t lds;
+    };
+    static const Shape shapes[] = {{dbslmm_gram_i8, 4, 256, 0},
+                                   {dbslmm_gram_big, 1, 256, gram::kLdsBytes},
+                                   {dbslmm_gram_huge, 1, 512, gram::kHLdsBytes}};
+    const Shape& k = shapes[which];
+    hipLaunchKernelGGL(k.kernel, dim3((nt + k.tiles_per_wg - 1) / k.tiles_per_wg), dim3(k.threads), k.lds, st,
+                       p->d_img, p->kpad, p->d_slot_pos, p->img.n_rows, tiles, nt, p->d_row0, p->d_m, p->d_ld,
+                       p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, static_cast<double>(p->n_ref),
+                       static_cast<double>(p->kpad - p->n_ref), p->tau, p->d_M, o.ncopy, p->M_elems, o.tmin_copy,
+                       o.tcopy, o.g16, o.off16, o.ld16);
+    return hipGetLastError();
+}
+
 // One run on the PCG route: statistics + Gram (the integer Gram as uint16 where it fits, Sigma in fp64
 // for the other blocks), then the iterations of every block and copy together.
 static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     dbslmm_ctx* ctx = p->ctx;
 #ifdef DBSLMM_DIAG
-    {
+    auto diag_error = [](const char* when) {
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fprintf(stderr, "run_pcg: stale error on entry: %s\n", hipGetErrorString(e));
-    }
+        if (e != hipSuccess) fprintf(stderr, "run_pcg: %s: %s\n", when, hipGetErrorString(e));
+    };
+#else
+    auto diag_error = [](const char*) {};
 #endif
+    diag_error("stale error on entry");
     if (const int rc = ensure_copies(p, n, 1)) return rc;
-#ifdef DBSLMM_DIAG
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fprintf(stderr, "run_pcg: error after ensure_copies: %s\n", hipGetErrorString(e));
-    }
-#endif
+    diag_error("error after ensure_copies");
     if (const int rc = pcg_layout(p, n)) return rc;
-#ifdef DBSLMM_DIAG
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fprintf(stderr, "run_pcg: error after pcg_layout: %s\n", hipGetErrorString(e));
-    }
-#endif
+    diag_error("error after pcg_layout");
     // results streamed to the host while the run iterates: dbslmm_plan_run_multi on one device
     p->so_active = p->so_want && p->stream_out;
     if (p->so_active)
         if (const int rc = so_prepare(p, n)) return rc;
     hipStream_t s = ctx->stream;
     hipEvent_t* ev = nullptr;
-    if (p->timing) {
-        const size_t need = kEvPerRun * static_cast<size_t>(p->runs_pending + 1);
-        while (p->ev.size() < need) {
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            p->ev.push_back(e);
-        }
-        ev = &p->ev[kEvPerRun * p->runs_pending];
-        p->runs_pending++;
-        p->run_route.resize(p->runs_pending);
-        p->run_route.back() = 1;
-    }
-    p->pcg_ev_end = ev ? ev[7] : nullptr;
+    if (const int rc = open_timed_run(p, true, &ev)) return rc;
+    p->pcg_ev_end = ev ? ev[kEvEnd] : nullptr;
     p->trsv_failed = false;
     p->stopped = false;
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[0], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvStart], s));
     // One launch in front of the Gram: the statistics, and with them the run's resets (status,
     // the count of iterating blocks, dbslmm_pcg_block's sequence counter) and the copies' shifts.
-    // The timed instants of this route are events 0, 1, 2, 3, 4 and 7 (collect_timing).
+    // The timed instants of this route: kEvStart, kEvStatsEnd, kEvGramEnd, kEvPcgBlockBegin / End and
+    // kEvEnd (collect_timing).
     static_assert(pcg::kMaxNC <= kFrontCopies, "PcgFront carries every copy's shift");
     PcgFront fr{};
     for (int c = 0; c < n; ++c) fr.shift[c] = 1.0 / (sigmas[c] * static_cast<double>(p->n_obs));
@@ -2497,34 +1972,18 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     hipLaunchKernelGGL(dbslmm_pcg_front, dim3(std::max(1, (p->n_slots + 255) / 256)), dim3(256), 0, s, p->img.rows(),
                        p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd, p->d_flags, fr);
     HIP_TRY(ctx, hipGetLastError());
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvStatsEnd], s));
     uint16_t* g16 = p->pcg_g16 ? p->d_G16 : nullptr;
-    const double nrd = static_cast<double>(p->n_ref), padk = static_cast<double>(p->kpad - p->n_ref);
-    // the Gram of tile lists (i8, big, huge) on stream st
-    auto gram = [&](hipStream_t st, const GramTile* ti, int32_t nt, const GramTile* tb, int32_t nb,
-                    const GramTile* th, int32_t nh) {
-        if (nh > 0)
-            hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nh), dim3(512), gram::kHLdsBytes, st, p->d_img, p->kpad,
-                               p->d_slot_pos, p->img.n_rows, th, nh,
-                               p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd,
-                               padk, p->tau, p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
-        if (nt > 0)
-            hipLaunchKernelGGL(dbslmm_gram_i8, dim3((nt + 3) / 4), dim3(256), 0, st, p->d_img, p->kpad, p->d_slot_pos,
-                               p->img.n_rows, ti, nt, p->d_row0,
-                               p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd, padk, p->tau,
-                               p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
-        if (nb > 0)
-            hipLaunchKernelGGL(dbslmm_gram_big, dim3(nb), dim3(256), gram::kLdsBytes, st, p->d_img, p->kpad,
-                               p->d_slot_pos, p->img.n_rows, tb, nb,
-                               p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd, nrd,
-                               padk, p->tau, p->d_M, 1, p->M_elems, INT32_MAX, -1, g16, p->d_off16, p->d_ld16);
-        return hipGetLastError();
-    };
+    const double nrd = static_cast<double>(p->n_ref);
+    // one copy of Sigma, and the integer Gram as uint16 where it fits
+    const GramOut go{1, INT32_MAX, -1, g16, p->d_off16, p->d_ld16};
     // (Measured and dropped: the Gram of the blocks dbslmm_pcg_block solves on the second stream
     // beside the chip-wide iterations -- its 256-tile workgroups hold 128 KiB of LDS, so the product
     // items cannot run beside them: config 4 8.8 -> 9.6 ms.)
-    HIP_TRY(ctx, gram(s, p->d_tiles, p->n_tiles, p->d_btiles, p->n_btiles, p->d_htiles, p->n_htiles));
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[2], s));
+    HIP_TRY(ctx, launch_gram(p, s, kGramHuge, p->d_htiles, p->n_htiles, go));
+    HIP_TRY(ctx, launch_gram(p, s, kGramI8, p->d_tiles, p->n_tiles, go));
+    HIP_TRY(ctx, launch_gram(p, s, kGramBig, p->d_btiles, p->n_btiles, go));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvGramEnd], s));
     PcgArgs a{};
     a.blk = p->d_pblk;
     a.G16 = g16;
@@ -2592,7 +2051,7 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     if (p->n_pflist > 0) {   // the small blocks' whole solves beside the chip-wide iterations
         HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->fork, 0));
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[3], ctx->stream2));   // dbslmm_pcg_block's span: 3 -> 4
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvPcgBlockBegin], ctx->stream2));
         // one workgroup per CU (its LDS holds x and p: one fits): the chip-wide kernels of the
         // other blocks keep the rest of every CU
         // (two per CU at one copy, where their LDS fits: configs 3 / 5 6.02 -> 6.27 / 2.35 -> 2.51 ms)
@@ -2601,11 +2060,11 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
         hipLaunchKernelGGL(dbslmm_pcg_block, dim3(grid), dim3(pcg::kThreads), pcg::block_lds_bytes(n), ctx->stream2, a,
                            p->d_pflist, p->n_pflist, p->d_pfnext, p->pcg_maxit);
         HIP_TRY(ctx, hipGetLastError());
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[4], ctx->stream2));
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvPcgBlockEnd], ctx->stream2));
         HIP_TRY(ctx, hipEventRecord(ctx->join, ctx->stream2));
         p->pcg_join = true;
-    } else if (ev) {
-        for (int k : {3, 4}) HIP_TRY(ctx, hipEventRecord(ev[k], s));
+    } else if (const int rc = record_instants(ctx, ev, {kEvPcgBlockBegin, kEvPcgBlockEnd}, s)) {
+        return rc;
     }
     p->pcg_it = 0;
     p->pcg_pending = true;
@@ -2627,19 +2086,18 @@ static int run_pcg(dbslmm_plan* p, const double* sigmas, int n) {
     return DBSLMM_OK;
 }
 
-// One run: statistics + Gram (front; else the Gram of the previous front run is reused), then n
-// factorisations + solves of it, copy c with sigma_s = sigmas[c] (n > 1: h2f tuning; copies
-// 1.. are device copies of the Gram, all factored by one merged tiled sequence).
-static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
+// One run: statistics + Gram, then n factorisations + solves of it, copy c with
+// sigma_s = sigmas[c] (n > 1: h2f tuning; copies 1.. are device copies of the Gram, all factored
+// by one merged tiled sequence).
+static int run_impl(dbslmm_plan* p, const double* sigmas, int n) {
     dbslmm_ctx* ctx = p->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (const int rc = pcg_finish(p)) return rc;   // a PCG run still pending (plan_run without sync)
-    if (front && pcg_route(p, sigmas, n)) return run_pcg(p, sigmas, n);
+    if (pcg_route(p, sigmas, n)) return run_pcg(p, sigmas, n);
     // A run kept off the PCG route by its number of copies alone keeps that route's accuracy: its
     // iterated h2f copies stop at pcg_tol (relative error per block and copy, as run_pcg), so a
     // fifth h2f factor does not move the results of the others from 1e-12 to cheb_tol.
-    p->h2f_tol = front && n > pcg::kMaxNC && pcg_eligible(p, sigmas, n) ? std::min(p->cheb_tol, p->pcg_tol)
-                                                                         : p->cheb_tol;
+    p->h2f_tol = n > pcg::kMaxNC && pcg_eligible(p, sigmas, n) ? std::min(p->cheb_tol, p->pcg_tol) : p->cheb_tol;
     if (const int rc = ensure_copies(p, n, n)) return rc;
     if (n > 1) {
         if (p->multi_n != n) {
@@ -2658,7 +2116,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     // h2f: the tiled blocks are factored once (copy cp.base) and the other copies iterate on it
     p->trsv_failed = false;
     ChebPlan cp;
-    const bool cheb = front && p->n_nonempty > 0 && cheb_plan(p, sigmas, n, cp);
+    const bool cheb = p->n_nonempty > 0 && cheb_plan(p, sigmas, n, cp);
     const int32_t tcopy = cheb ? cp.base : -1;   // Gram epilogues: iterated blocks write this copy only
     // ... the blocks with m >= tmin_copy: the tiled ones and the single-workgroup ones (ld > 64),
     // whose other h2f copies iterate on the base factor too (dbslmm_chol_cheb)
@@ -2666,18 +2124,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
     const int32_t tmin_copy = large_cheb ? chol::kSmallLd : p->tiled_min;
     hipStream_t s = ctx->stream;
     hipEvent_t* ev = nullptr;
-    if (p->timing) {
-        const size_t need = kEvPerRun * static_cast<size_t>(p->runs_pending + 1);
-        while (p->ev.size() < need) {
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            p->ev.push_back(e);
-        }
-        ev = &p->ev[kEvPerRun * p->runs_pending];
-        p->runs_pending++;
-        p->run_route.resize(p->runs_pending);
-        p->run_route.back() = 0;
-    }
+    if (const int rc = open_timed_run(p, false, &ev)) return rc;
     p->pcg_ran = false;
     p->pcg_pending_var = false;
     const size_t nbk = static_cast<size_t>(p->nbk);
@@ -2693,22 +2140,20 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         p->trsv_epoch = 0;
     }
     p->stopped = false;
-    if (front) HIP_TRY(ctx, hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), s));
+    HIP_TRY(ctx, hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), s));
     HIP_TRY(ctx, hipMemsetAsync(p->d_status, 0, n * nbk * sizeof(int32_t), s));
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[0], s));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvStart], s));
     // the statistics of every slot in one launch (a gather from the image's row table: microseconds,
     // so a lead group's Gram right behind it starts at once)
-    if (front && p->n_slots > 0) {
+    if (p->n_slots > 0) {
         hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, s, p->img.rows(),
                            p->n_ref, p->d_slot_pos, p->d_slot_block, p->n_slots, p->d_S, p->d_mu, p->d_rsd,
                            p->d_flags);
         HIP_TRY(ctx, hipGetLastError());
     }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[9], s));
-    if (!front && n > 1)
-        return (ctx->err = "a multi-copy run needs the Gram front", DBSLMM_E_STATE);
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvLeadGramBegin], s));
     const std::vector<TLaunch>& tl = n > 1 && !cheb ? p->tl_multi : p->tl;
-    // lead group (plan_create): the single-copy sequence is split in two -- the lead blocks'
+    // lead group (plan_layout.hpp): the single-copy sequence is split in two -- the lead blocks'
     // sequence starts on stream2 right after their Gram tiles, the rest on stream4 after the
     // whole Gram; stream2 waits for the rest before the substitutions
     const bool lead = !p->tl_rest.empty() && (n == 1 || cheb);
@@ -2724,18 +2169,10 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
             if (rc != DBSLMM_OK) return rc;
         }
     }
-    auto gram_huge = [&](int32_t t0, int32_t nt) {
-        hipLaunchKernelGGL(dbslmm_gram_huge, dim3(nt), dim3(512), gram::kHLdsBytes, s, p->d_img,
-                           p->kpad, p->d_slot_pos, p->img.n_rows, p->d_htiles + t0, nt, p->d_row0, p->d_m, p->d_ld,
-                           p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd,
-                           static_cast<double>(p->n_ref), static_cast<double>(p->kpad - p->n_ref),
-                           p->tau, p->d_M, n, p->M_elems, tmin_copy, tcopy, nullptr, nullptr, nullptr);
-    };
-    if (front && p->n_htiles_lead > 0) {
-        gram_huge(0, p->n_htiles_lead);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[10], s));
+    // (the factorisation overwrites its matrix: the Gram epilogues write all n copies)
+    const GramOut go{n, tmin_copy, tcopy, nullptr, nullptr, nullptr};
+    HIP_TRY(ctx, launch_gram(p, s, kGramHuge, p->d_htiles, p->n_htiles_lead, go));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvLeadGramEnd], s));
     // the lead sequence (stream2, high priority: the critical path) waits for this point of the
     // main stream; its graph is launched after every main-stream kernel is enqueued (a graph
     // launch of a few hundred nodes keeps the host busy for milliseconds)
@@ -2743,44 +2180,21 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
         HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
         debug_spin(p, s, 1);
     }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));   // (statistics = 0 -> 1 less the lead Gram 9 -> 10)
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvStatsEnd], s));   // (the statistics span less the lead Gram's)
     // the other tiled blocks' Gram tiles next: with early_fork their sequence (and the single
     // sequence without a lead group) forks here, before the non-tiled blocks' Gram
-    if (front && p->n_htiles_tiled > p->n_htiles_lead) {
-        gram_huge(p->n_htiles_lead, p->n_htiles_tiled - p->n_htiles_lead);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    HIP_TRY(ctx, launch_gram(p, s, kGramHuge, p->d_htiles + p->n_htiles_lead, p->n_htiles_tiled - p->n_htiles_lead, go));
     const bool early = p->early_fork && p->n_nonempty > 0;
     if (early) {
         HIP_TRY(ctx, hipEventRecord(ctx->fork2, s));
         HIP_TRY(ctx, hipStreamWaitEvent(lead ? ctx->stream4 : ctx->stream2, ctx->fork2, 0));
     }
-    if (front && p->n_tiles > 0) {
-        dim3 grid((p->n_tiles + 3) / 4);
-        hipLaunchKernelGGL(dbslmm_gram_i8, grid, dim3(256), 0, s, p->d_img, p->kpad,
-                           p->d_slot_pos, p->img.n_rows, p->d_tiles, p->n_tiles, p->d_row0, p->d_m, p->d_ld, p->d_matoff, p->d_flags, p->d_S,
-                           p->d_mu, p->d_rsd, static_cast<double>(p->n_ref),
-                           static_cast<double>(p->kpad - p->n_ref), p->tau, p->d_M, n, p->M_elems,
-                           tmin_copy, tcopy, nullptr, nullptr, nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (front && p->n_htiles > p->n_htiles_tiled) {
-        gram_huge(p->n_htiles_tiled, p->n_htiles - p->n_htiles_tiled);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (front && p->n_btiles > 0) {
-        hipLaunchKernelGGL(dbslmm_gram_big, dim3(p->n_btiles), dim3(256), gram::kLdsBytes, s, p->d_img,
-                           p->kpad, p->d_slot_pos, p->img.n_rows, p->d_btiles, p->n_btiles, p->d_row0, p->d_m, p->d_ld,
-                           p->d_matoff, p->d_flags, p->d_S, p->d_mu, p->d_rsd,
-                           static_cast<double>(p->n_ref), static_cast<double>(p->kpad - p->n_ref),
-                           p->tau, p->d_M, n, p->M_elems, tmin_copy, tcopy, nullptr, nullptr, nullptr);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    // (the factorisation overwrites its matrix: the Gram epilogues write all n copies)
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev[2], s));
+    HIP_TRY(ctx, launch_gram(p, s, kGramI8, p->d_tiles, p->n_tiles, go));
+    HIP_TRY(ctx, launch_gram(p, s, kGramHuge, p->d_htiles + p->n_htiles_tiled, p->n_htiles - p->n_htiles_tiled, go));
+    HIP_TRY(ctx, launch_gram(p, s, kGramBig, p->d_btiles, p->n_btiles, go));
+    if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvGramEnd], s));
     if (p->debug_stop == 1) {   // tests: the block matrices hold Sigma (dbslmm_plan_block_matrix)
-        for (int k : {3, 4, 5, 6, 8, 11, 7})
-            if (ev) HIP_TRY(ctx, hipEventRecord(ev[k], s));
+        if (const int rc = record_instants(ctx, ev, kEvAfterGram, s)) return rc;
         p->ran = true;
         p->stopped = true;      // download / variance refuse: the betas of this run were never computed
         return DBSLMM_OK;
@@ -2828,11 +2242,11 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                 HIP_TRY(ctx, hipGetLastError());
             }
         }
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[3], s));
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvLargeEnd], s));
         // single-wave blocks: concurrently on stream2 when there is no tiled sequence, else
         // behind the single-workgroup kernel (each stream keeps its own hardware queue)
         hipStream_t ss = tl.empty() ? ctx->stream2 : s;
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[4], ss));
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvSmallBegin], ss));
         for (int c = 0; c < n && p->n_small > 0; ++c) {
             const unsigned g = static_cast<unsigned>((p->n_small + chol::kSmallWaves - 1) / chol::kSmallWaves);
             hipLaunchKernelGGL(dbslmm_chol_small, dim3(g), dim3(chol::kSmallWaves * chol::kWave), 0,
@@ -2842,18 +2256,18 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                                p->d_beta_l + c * p->n_l, p->d_status + c * p->nbk);
             HIP_TRY(ctx, hipGetLastError());
         }
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[5], ss));
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvSmallEnd], ss));
         if (ss != s) HIP_TRY(ctx, hipEventRecord(ctx->join, ss));
         if (lead) {
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->fork, 0));
-            if (ev) HIP_TRY(ctx, hipEventRecord(ev[6], ctx->stream2));
+            if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvTiledBegin], ctx->stream2));
             debug_spin(p, ctx->stream2, -1);
             debug_spin(p, ctx->stream4, 1);
             int rc = run_tiled_copy(p, isn, fcopy);
             if (rc == DBSLMM_OK) rc = run_rest_copy(p, isn, fcopy);
             if (rc != DBSLMM_OK) return rc;
         } else if (ev) {
-            HIP_TRY(ctx, hipEventRecord(ev[6], ctx->stream2));
+            HIP_TRY(ctx, hipEventRecord(ev[kEvTiledBegin], ctx->stream2));
         }
         if (!tl.empty()) {
             // the tiled sequence (~2.5 launches per 128 columns) is replayed from a graph
@@ -2866,13 +2280,13 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                     // factorisation, the lead group's on stream2 after the lead factorisation
                     const TGroup gr = tgroup_rest(p), gl = tgroup_lead(p);
                     if (rc == DBSLMM_OK && gr.n_items > 0) rc = run_pbwd(p, isn, fcopy, gr);
-                    if (ev && cheb) HIP_TRY(ctx, hipEventRecord(ev[11], gr.st));
+                    if (ev && cheb) HIP_TRY(ctx, hipEventRecord(ev[kEvRestEnd], gr.st));
                     if (rc == DBSLMM_OK && cheb && gr.n_items > 0)
                         rc = p->sub_block ? run_tcheb(p, isn, cp, gr.st) : run_cheb(p, isn, cp, gr);
                     if (rc == DBSLMM_OK) rc = run_pbwd(p, isn, fcopy, gl);
                     if (rc != DBSLMM_OK) return rc;
                     if (cheb) {
-                        if (ev) HIP_TRY(ctx, hipEventRecord(ev[8], ctx->stream2));
+                        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvTiledEnd], ctx->stream2));
                         rc = run_cheb(p, isn, cp, gl);
                         if (rc != DBSLMM_OK) return rc;
                     }
@@ -2887,8 +2301,7 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                     if (rc == DBSLMM_OK) rc = run_pbwd(p, isn, fcopy, tgroup_all(p));
                     if (rc != DBSLMM_OK) return rc;
                     if (cheb) {
-                        if (ev) HIP_TRY(ctx, hipEventRecord(ev[8], ctx->stream2));
-                        if (ev) HIP_TRY(ctx, hipEventRecord(ev[11], ctx->stream2));
+                        if (const int rce = record_instants(ctx, ev, {kEvTiledEnd, kEvRestEnd}, ctx->stream2)) return rce;
                         rc = run_cheb(p, isn, cp, tgroup_all(p));
                         if (rc != DBSLMM_OK) return rc;
                     }
@@ -2900,21 +2313,15 @@ static int run_impl(dbslmm_plan* p, bool front, const double* sigmas, int n) {
                 if (rc != DBSLMM_OK) return rc;
             }
         }
-        if (ev && !cheb) HIP_TRY(ctx, hipEventRecord(ev[8], ctx->stream2));
-        if (ev && !cheb) HIP_TRY(ctx, hipEventRecord(ev[11], ctx->stream2));
-        if (ev) HIP_TRY(ctx, hipEventRecord(ev[7], ctx->stream2));
+        if (!cheb)
+            if (const int rc = record_instants(ctx, ev, {kEvTiledEnd, kEvRestEnd}, ctx->stream2)) return rc;
+        if (ev) HIP_TRY(ctx, hipEventRecord(ev[kEvEnd], ctx->stream2));
         HIP_TRY(ctx, hipEventRecord(ctx->join3, ctx->stream2));
         if (ss != s) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join, 0));
         HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join3, 0));
     }
-    else if (ev) {   // no blocks: keep the event set complete
-        HIP_TRY(ctx, hipEventRecord(ev[3], s));
-        HIP_TRY(ctx, hipEventRecord(ev[4], s));
-        HIP_TRY(ctx, hipEventRecord(ev[5], s));
-        HIP_TRY(ctx, hipEventRecord(ev[6], s));
-        HIP_TRY(ctx, hipEventRecord(ev[8], s));
-        HIP_TRY(ctx, hipEventRecord(ev[11], s));
-        HIP_TRY(ctx, hipEventRecord(ev[7], s));
+    else if (const int rc = record_instants(ctx, ev, kEvAfterGram, s)) {   // no blocks
+        return rc;
     }
     p->ran = true;
     p->n_runs++;
@@ -3102,7 +2509,7 @@ static int download_copy(dbslmm_plan* p, int c, double* beta_s, double* beta_l, 
 int dbslmm_plan_run(dbslmm_plan* p) {
     if (!p) return DBSLMM_E_ARG;
     if (p->mp) return mp_run(p, &p->sigma_s, 1, false);
-    return run_impl(p, true, &p->sigma_s, 1);
+    return run_impl(p, &p->sigma_s, 1);
 }
 
 // h2f tuning (software/DBSLMM.R:204-219 runs dbslmm once per h2 factor): one statistics pass + Gram, then
@@ -3125,7 +2532,7 @@ int dbslmm_plan_run_multi(dbslmm_plan* p, const double* sigmas, int32_t n_sigma,
     ARG_CHECK(ctx, static_cast<int64_t>(p->n_nonempty) * n_sigma < 32768,
               "blocks x sigmas must stay below 32768 (packed work items)");
     p->so_want = true;                       // (the PCG route may stream its results: stream_out)
-    int rc = run_impl(p, true, sigmas, n_sigma);
+    int rc = run_impl(p, sigmas, n_sigma);
     p->so_want = false;
     if (!rc && p->pcg_ran && p->so_active) return stream_results(p, beta_s, beta_l, block_status);
     if (!rc) rc = dbslmm_plan_sync(p);
@@ -3306,7 +2713,7 @@ static int variance_factor(dbslmm_plan* p) {
     p->cheb_pending_var = false;
     p->pcg_pending_var = false;
     p->force_factor = true;          // the variance needs the factor of this sigma
-    const int rc = run_impl(p, true, &sg, 1);
+    const int rc = run_impl(p, &sg, 1);
     p->force_factor = false;
     return rc;
 }

@@ -39,9 +39,10 @@
 // Factor layout (chol_tiled.hip): strict lower = L; each 64 x 64 diagonal tile holds, on and
 // above its diagonal, X^T with X = L_kk^{-1}; every other 64 x 64 tile of the upper triangle holds
 // the transposed L tile (L^T), so the backward substitution streams rows like the forward one.
+#include "dims.hpp"
+
 namespace trsv {
 
-constexpr int kT = 64;                       // tile rows = the stored diagonal inverse blocks
 constexpr int kSW = 8;                       // streaming waves (rows 8 w .. 8 w + 7 of a tile)
 constexpr int kThreads = (kSW + 1) * 64;     // + the control wave
 constexpr int kPF = 4;                       // column tiles of L in flight per streaming wave

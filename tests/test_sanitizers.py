@@ -4,6 +4,8 @@
   (`make -C dbslmm_amd/csrc sanitize`): argument handling and the whole host pipeline --
   .fam/.bim/summary/block readers, allele + MAF matching, addBlock, CSR assembly, .badsnps
   writer -- through --dry-run (stops before the first GPU call);
+* the plan's host layout (dbslmm_amd/csrc/plan_layout.hpp) through its stand-alone check
+  (tests/host/layout_check.cpp, built by the same target as `layout_asan`);
 * the CPU oracle (`make -C oracle sanitize`): a standalone driver over every oracle entry point
   on the reference's test_dat panel and a synthetic panel with missing calls and n % 4 = 3.
 
@@ -90,6 +92,13 @@ def test_valid_argument_handling_under_asan_ubsan(valid_asan, args, tmp_path):
     r = _run(valid_asan, args, cwd=str(tmp_path))
     assert _clean(r), r.stderr[-3000:]
     assert r.returncode in (0, 1), (r.returncode, r.stderr[-3000:])
+
+
+def test_plan_layout_under_asan_ubsan():
+    exe = _built(os.path.join(ROOT, "dbslmm_amd", "csrc"), "sanitize", os.path.join(BIN, "layout_asan"))
+    r = _run(exe, [])
+    assert _clean(r), r.stderr[-3000:]
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("bed,n_ref,n_snp", [

@@ -44,7 +44,7 @@ nreg = (m + 127) // 128
 print("m", m, "regions", nreg, "per run (ms):", {k: round(v / max(nrun, 1), 3) for k, v in zip(_lib.KERNEL_NAMES, ms)})
 if STAMPS:
     L.dbslmm_debug_stamps(out.ctypes.data_as(C.c_void_p))
-    R = 4 if m >= 4096 else 2                      # regions per super step (plan.hip kWideMin)
+    R = 4 if m >= 4096 else 2                      # regions per super step (plan_layout.hpp kWideMin)
     n_first = max(0, (nreg - 1) // R)               # first regions of super steps 1.. (no pending update)
     for lab, ph, n in (("other regions", out[:8], nreg - n_first), ("first of super step", out[8:16], n_first)):
         ph = ph / reps / max(n, 1) / 1e3
