@@ -1036,38 +1036,49 @@ extern "C" __global__ __launch_bounds__(256) void dbslmm_valid_partial(
     const uint8_t* __restrict__ img, int32_t n_ref, int64_t pitch,
     const int64_t* __restrict__ ptr, const int32_t* __restrict__ pos,
     const double* __restrict__ z1, const double* __restrict__ mu, const double* __restrict__ rsd,
-    double* __restrict__ partial, int32_t n_chunks) {
+    double* __restrict__ partial, int32_t n_chunks, int32_t num_block) {
     __shared__ double red[256 / kWave];
-    const int b = blockIdx.y;
     const int64_t w = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t n_words = (n_ref + 15) / 16;
-    double y[16];
+    const int nv = static_cast<int>(min<int64_t>(16, n_ref - 16 * w));
+    // grid row y takes the blocks y, y + gridDim.y, ...: the launch caps gridDim.y (kValidGridY),
+    // so the number of blocks is not bound by the device's grid-row limit.  A block's sums do not
+    // depend on which grid row computes them.
+    for (int b = blockIdx.y; b < num_block; b += gridDim.y) {
+        double y[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) y[i] = 0.0;
-    if (w < n_words) {
-        const int nv = static_cast<int>(min<int64_t>(16, n_ref - 16 * w));
-        for (int64_t j = ptr[b]; j < ptr[b + 1]; ++j) {
-            const uint32_t word = *reinterpret_cast<const uint32_t*>(img + static_cast<int64_t>(pos[j]) * pitch + 4 * w);
-            const double m0 = mu[j], wt = z1[j] * rsd[j];
+        for (int i = 0; i < 16; ++i) y[i] = 0.0;
+        if (w < n_words) {
+            for (int64_t j = ptr[b]; j < ptr[b + 1]; ++j) {
+                // the row's four possible terms (g - mu) z1 / sd, each product rounded on its own and
+                // then only added (no FMA into y): a row that enters twice with weights +a and -a
+                // cancels term by term.  A missing call is (mu - mu) wt: 0, or NaN on a row
+                // without a finite sd, as 0 * NaN is in the reference.
+#pragma clang fp contract(off)
+                const uint32_t word = *reinterpret_cast<const uint32_t*>(img + static_cast<int64_t>(pos[j]) * pitch + 4 * w);
+                const double m0 = mu[j], wt = z1[j] * rsd[j];
+                const double t2 = (2.0 - m0) * wt, t1 = (1.0 - m0) * wt, t0 = (0.0 - m0) * wt, tm = (m0 - m0) * wt;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const uint32_t code = (word >> (2 * i)) & 3u;
-                // 00 -> 2, 10 -> 1, 11 -> 0, 01 -> missing (the mean: contributes 0)
-                const double g = code == 0 ? 2.0 : (code == 2 ? 1.0 : (code == 3 ? 0.0 : m0));
-                if (i < nv) y[i] += (g - m0) * wt;
+                for (int i = 0; i < 16; ++i) {
+                    const uint32_t code = (word >> (2 * i)) & 3u;
+                    // 00 -> 2, 10 -> 1, 11 -> 0, 01 -> missing (the mean: contributes 0)
+                    const double t = code == 0 ? t2 : (code == 2 ? t1 : (code == 3 ? t0 : tm));
+                    if (i < nv) y[i] += t;
+                }
             }
         }
-    }
-    double s = 0.0;
+        double s = 0.0;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s += y[i] * y[i];
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int q = 0; q < 256 / kWave; ++q) t += red[q];
-        partial[static_cast<int64_t>(b) * n_chunks + blockIdx.x] = t;
+        for (int i = 0; i < 16; ++i) s += y[i] * y[i];
+        for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
+        if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0.0;
+            for (int q = 0; q < 256 / kWave; ++q) t += red[q];
+            partial[static_cast<int64_t>(b) * n_chunks + blockIdx.x] = t;
+        }
+        __syncthreads();            // red is written again by the next block of this grid row
     }
 }
 

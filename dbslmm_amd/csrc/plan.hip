@@ -3191,8 +3191,11 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
             hipLaunchKernelGGL(dbslmm_slot_stats, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
                                ctx->stream, im.rows(), n_ref, d_pos, nullptr, static_cast<int32_t>(n_rows),
                                nullptr, d_mu, d_rsd, nullptr);
-        hipLaunchKernelGGL(dbslmm_valid_partial, dim3(n_chunks, num_block), dim3(256), 0, ctx->stream,
-                           db, n_ref, im.pitch, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks);
+        // grid rows stride over the blocks, so num_block is not bound by the grid-row limit
+        constexpr int32_t kValidGridY = 65535;
+        hipLaunchKernelGGL(dbslmm_valid_partial, dim3(n_chunks, std::min(num_block, kValidGridY)), dim3(256), 0,
+                           ctx->stream, db, n_ref, im.pitch, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks,
+                           num_block);
         hipLaunchKernelGGL(dbslmm_valid_reduce, dim3((num_block + 255) / 256), dim3(256), 0, ctx->stream,
                            d_part, n_chunks, num_block, static_cast<double>(n_ref), d_deno);
         if ((e = hipGetLastError()) != hipSuccess ||
