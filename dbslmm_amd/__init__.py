@@ -8,6 +8,8 @@ entry points mirror the reference operator interface (fboehm/DBSLMM, scr/dbslmmf
 * ``Plan``                -- the same problem kept resident in HBM for repeated solves.
 * ``bed_maf``             -- the MAF pass of IO::readBim (dtpr.cpp:93-102).
 * ``read_snp_std``        -- IO::readSNPIm + SNPPROC::nomalizeVec for a list of rows.
+* ``clump``               -- the index SNPs of a candidate list by PLINK's greedy clumping rule on the
+  reference panel (software/DBSLMM.R:139-145), ``ld_r2`` the dense r2 matrix of a list of rows.
 * ``Plan.score``          -- the polygenic scores of a target panel for every h2f copy of the latest
   run (what the reference leaves to ``plink --score``), ``tune_r2`` the R2 index of TUNE.R on them.
 * ``Context.row_stats``   -- the exact per-row integers (sum, sum of squares, missing calls) the
@@ -26,7 +28,7 @@ from . import _lib
 from ._lib import (WORKLOAD_LEN, BLOCK_EMPTY, BLOCK_MONOMORPHIC, BLOCK_NOT_CONVERGED, BLOCK_NOT_PD,
                    BLOCK_OK, KERNEL_NAMES, SOLVER_AUTO, SOLVER_FACTOR, SOLVER_PCG, DbslmmError)
 
-__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2",
+__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2", "ld_r2", "clump",
            "DbslmmError", "BLOCK_OK", "BLOCK_EMPTY", "BLOCK_NOT_PD", "BLOCK_MONOMORPHIC",
            "BLOCK_NOT_CONVERGED", "KERNEL_NAMES", "SOLVER_AUTO", "SOLVER_FACTOR", "SOLVER_PCG"]
 
@@ -415,6 +417,36 @@ def valid_blocks(ctx: Context, bed: np.ndarray, n_ref: int, ptr, pos, z1, z2):
     ctx.check(ctx.lib.dbslmm_valid_blocks(ctx.h, _ptr(bed), bed.size, n_ref, nb, _ptr(ptr), _ptr(pos),
                                           _ptr(z1), _ptr(z2), _ptr(nume), _ptr(deno)), "valid_blocks")
     return nume, deno
+
+
+def ld_r2(ctx: Context, bed: np.ndarray, n_ref: int, rows) -> np.ndarray:
+    """r2 of every pair of the bed rows `rows` (dbslmm_ld_r2): the squared Pearson correlation of the
+    dosages, missing calls at the row mean; NaN in the row and column of a row without variance."""
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    out = np.zeros((len(rows), len(rows)))
+    ctx.check(ctx.lib.dbslmm_ld_r2(ctx.h, _ptr(bed), bed.size, n_ref, _ptr(rows), len(rows), _ptr(out)), "ld_r2")
+    return out
+
+
+def clump(ctx: Context, bed: np.ndarray, n_ref: int, rows, chrom, bp, r2: float = 0.2, kb: float = 1000) -> np.ndarray:
+    """PLINK's greedy clumping (dbslmm_clump) of the candidates `rows` (bed rows, most significant
+    first) with chromosome codes `chrom` and base pairs `bp`: index_of[k] = the candidate that
+    absorbed k, k itself for an index SNP.  The event time of the tile kernel is kept in
+    ctx.clump_gpu_ms."""
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    chrom = np.ascontiguousarray(chrom, dtype=np.int32)
+    bp = np.ascontiguousarray(bp, dtype=np.int64)
+    if not (rows.shape == chrom.shape == bp.shape and rows.ndim == 1):
+        raise ValueError("rows, chrom, bp: one entry per candidate")
+    out = np.zeros(max(1, len(rows)), dtype=np.int32)
+    ms = np.zeros(1)
+    args = _lib.ClumpArgs(float(r2), int(round(float(kb) * 1000)))
+    ctx.check(ctx.lib.dbslmm_clump(ctx.h, _ptr(bed), bed.size, n_ref, len(rows), _ptr(rows), _ptr(chrom), _ptr(bp),
+                                   C.byref(args), _ptr(out), None, _ptr(ms)), "clump")
+    ctx.clump_gpu_ms = float(ms[0])
+    return out[:len(rows)]
 
 
 def tune_r2(scores, pheno) -> tuple[np.ndarray, int]:

@@ -22,9 +22,10 @@ EXPORTS = (
     "dbslmm_ctx_cache_bed", "dbslmm_ctx_cache_bed_fd", "dbslmm_plan_block_matrix",
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
     "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges", "dbslmm_plan_score",
+    "dbslmm_ld_r2", "dbslmm_clump",
 )
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
@@ -72,6 +73,11 @@ class ScoreArgs(C.Structure):
     ]
 
 
+class ClumpArgs(C.Structure):
+    """dbslmm_clump_args: the r2 threshold and the window in base pairs."""
+    _fields_ = [("r2", C.c_double), ("window_bp", C.c_int64)]
+
+
 _lib = None
 
 
@@ -114,6 +120,8 @@ def load(path: str | None = None):
     L.dbslmm_bed_maf.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int64, V]
     L.dbslmm_bed_row_stats.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int64, V]
     L.dbslmm_read_snp_std.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V, V]
+    L.dbslmm_ld_r2.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V]
+    L.dbslmm_clump.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, P(ClumpArgs), V, V, V]
     L.dbslmm_valid_blocks.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V, V, V]
     L.dbslmm_plan_variance.argtypes = [V, P(TestPanel), V, V]
     L.dbslmm_plan_score.argtypes = [V, P(TestPanel), P(ScoreArgs), C.c_int32, V, V, V, V]

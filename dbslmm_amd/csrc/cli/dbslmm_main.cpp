@@ -19,6 +19,10 @@
 // `plink --score <eff>.txt 1 2 4 sum`, Rmd/Manual.Rmd:176-188) and, with -h2f and phenotypes in
 // the .fam, the R2 of every factor and the best one to PREFIX.hval.r2 / PREFIX.hbest.r2
 // (software/TUNE.R, index r2).
+// --summary FILE --pth P [--clump-r2 0.2] [--clump-kb 1000] instead of -s / -l: the large-effect SNPs
+// are the index SNPs of PLINK's greedy clumping of the summary's significant SNPs on the reference
+// panel (software/DBSLMM.R:130-184, its `plink --clump` step on the GPU: dbslmm_clump), listed in
+// <eff>.clumped.txt; everything else is a small-effect SNP, and the run goes on as with -s / -l.
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <sys/time.h>
@@ -65,11 +69,16 @@ struct Param {                     // PARAM, scr/dbslmm.hpp:29-45 (initialised h
     int parse_threads = 8;          // --parse-threads N: host parser threads beside the GPU set-up
     string h2f;                     // "0.8,1,1.2": h2 factors of software/DBSLMM.R tuning
     string score;                   // --score PREFIX: polygenic scores of the -dat_str panel
+    string summary;                 // --summary FILE: the whole GEMMA summary, split by clumping
+    double pth = 0.0, clump_r2 = 0.2, clump_kb = 1000.0;   // --pth (plink --clump-p1), --clump-r2, --clump-kb
+    bool has_pth = false;
 };
 
 // The host rows keep string_views into the mmap'd input files (no per-SNP allocation).
 struct Bim {                        // map<string, ALLELE> of IO::readBim: line index = .bed row
     vector<string_view> snp, a1, a2;
+    vector<string_view> chr;        // field 1, and
+    vector<long> bp;                // field 4 (clumping: --summary)
     vector<char> bad;               // fewer than 6 fields: not inserted (the row still counts)
     vector<double> maf;             // GPU MAF pass (constr), else empty (0.0)
     StrIndex idx;                   // snp -> first line with it (std::map::insert keeps the first)
@@ -140,7 +149,14 @@ void print_help() {
               << " --score   [prefix]     scores of the -dat_str panel (its -test_indicator_file individuals, or\n"
               << "                        all) from the fitted effects, one column per -h2f factor, as\n"
               << "                        `plink --score <eff>.txt 1 2 4 sum`: <prefix>.score.txt; with -h2f and\n"
-              << "                        phenotypes in the .fam also <prefix>.hval.r2 / .hbest.r2 (extension)\n";
+              << "                        phenotypes in the .fam also <prefix>.hval.r2 / .hbest.r2 (extension)\n"
+              << " --summary [filename]   the whole summary data instead of -s / -l: the large effect SNPs are\n"
+              << "                        the index SNPs of clumping its SNPs with p <= --pth on the reference\n"
+              << "                        panel (plink --clump as software/DBSLMM.R runs it), listed in\n"
+              << "                        <eff>.clumped.txt (extension)\n"
+              << " --pth     [num]        --summary: significance threshold of the candidates (--clump-p1)\n"
+              << " --clump-r2 [num]       --summary: r2 threshold, default 0.2\n"
+              << " --clump-kb [num]       --summary: window in kb, default 1000\n";
 }
 
 // DBSLMM::Assign (scr/dbslmm.cpp:67-172): a flag's value is skipped when it starts with '-'.
@@ -178,6 +194,10 @@ void assign(int argc, char** argv, Param& p) {
         else if (is("--h2f", "-h2f")) { if ((v = take(i))) p.h2f = v; }
         else if (!strcmp(a, "--h2f-merged")) p.h2f_merged = true;
         else if (!strcmp(a, "--score")) { if ((v = take(i))) p.score = v; }
+        else if (!strcmp(a, "--summary")) { if ((v = take(i))) p.summary = v; }
+        else if (!strcmp(a, "--pth")) { if ((v = take(i))) { p.pth = atof(v); p.has_pth = true; } }
+        else if (!strcmp(a, "--clump-r2")) { if ((v = take(i))) p.clump_r2 = atof(v); }
+        else if (!strcmp(a, "--clump-kb")) { if ((v = take(i))) p.clump_kb = atof(v); }
         else if (!strcmp(a, "--dry-run")) p.dry_run = true;
         else if (!strcmp(a, "--timing")) p.timing = true;
         else if (!strcmp(a, "--repeat")) { if ((v = take(i))) p.repeat = std::max(0, atoi(v)); }
@@ -187,20 +207,23 @@ void assign(int argc, char** argv, Param& p) {
 
 // IO::readBim (scr/dtpr.cpp:83-123): fields 1 (SNP), 4 (a1), 5 (a2) of each tab-separated line,
 // parsed on several threads into views of the mapped file; the SNP index is built concurrently.
+// Fields 0 (chromosome) and 3 (bp) are kept for the clumping of --summary.
 bool read_bim(const MappedText& f, Bim& bim) {
     if (!f.ok) return false;
     const unsigned T = host_threads();
-    struct Row { string_view snp, a1, a2; bool ok; };
+    struct Row { string_view snp, a1, a2, chr, bp; bool ok; };
     vector<vector<Row>> part(T);
     const vector<size_t> cnt = parallel_lines(f.text, T, [&](unsigned t, string_view line) {
         string_view fl[6];
-        part[t].push_back(tab_fields(line, fl, 6) < 6 ? Row{{}, {}, {}, false} : Row{fl[1], fl[4], fl[5], true});
+        part[t].push_back(tab_fields(line, fl, 6) < 6 ? Row{{}, {}, {}, {}, {}, false} : Row{fl[1], fl[4], fl[5], fl[0], fl[3], true});
     });
     size_t n = 0;
     for (size_t c : cnt) n += c;
     bim.snp.resize(n);
     bim.a1.resize(n);
     bim.a2.resize(n);
+    bim.chr.resize(n);
+    bim.bp.assign(n, 0);
     bim.bad.assign(n, 0);
     vector<size_t> off(part.size() + 1, 0);
     for (size_t t = 0; t < part.size(); ++t) off[t + 1] = off[t] + part[t].size();
@@ -212,6 +235,8 @@ bool read_bim(const MappedText& f, Bim& bim) {
                 bim.snp[i] = r.snp;
                 bim.a1[i] = r.a1;
                 bim.a2[i] = r.a2;
+                bim.chr[i] = r.chr;
+                if (r.ok) bim.bp[i] = field_atol(r.bp);
                 bim.bad[i] = !r.ok;
             }
     });
@@ -655,6 +680,15 @@ int main(int argc, char** argv) {
               << "\n-b:      " << p.b << "\n-h:      " << p.h << "\n-t:      " << p.t
               << "\n-eff:    " << p.eff << "\n";
     // input checks of BatchRun (scr/dbslmm.cpp:195-227)
+    const bool clump_mode = !p.summary.empty();
+    if (clump_mode && (!p.s.empty() || !p.l.empty()))
+        return fail("--summary replaces -s / -l (the split comes from the clumping): give one or the other");
+    if (clump_mode && !p.has_pth) return fail("--summary needs --pth (the significance threshold of the candidates)");
+    if (!clump_mode && p.has_pth) return fail("--pth needs --summary");
+    if (clump_mode && !(p.pth > 0 && p.pth <= 1)) return fail("--pth must be in (0, 1]");
+    if (clump_mode && !(p.clump_r2 > 0 && p.clump_r2 <= 1)) return fail("--clump-r2 must be in (0, 1]");
+    if (clump_mode && !(p.clump_kb >= 0)) return fail("--clump-kb must not be negative");
+    if (clump_mode) p.s = p.summary;    // read as the small-effect file, then split
     if (p.s.empty()) return fail("-s is no parameter!");
     std::ifstream sf(p.s), lf(p.l), rf(p.r + ".fam"), bf(p.b);
     if (!bf) return fail(p.b + " dose not exist!");
@@ -668,7 +702,7 @@ int main(int argc, char** argv) {
     if (p.nsnp <= 0 || p.n <= 0) return fail("-n and -nsnp must be positive!");
     if (!p.score.empty() && p.dat_str.empty())
         return fail("--score needs -dat_str (the bfile of the panel to score)");
-    const bool has_lfile = static_cast<bool>(lf);
+    bool has_lfile = static_cast<bool>(lf);
     sf.close();
     lf.close();
     rf.close();
@@ -744,14 +778,14 @@ int main(int argc, char** argv) {
     const vector<Block> blocks = read_block(p.b);
     MappedText s_txt, l_txt;
     s_txt.open(p.s);
-    const vector<Summ> summ_s = read_summ(s_txt);
+    vector<Summ> summ_s = read_summ(s_txt);
     vector<Summ> summ_l;
     if (has_lfile) {
         l_txt.open(p.l);
         summ_l = read_summ(l_txt);
     }
-    const vector<int32_t> rows_s = lookup_ref(summ_s, bim);
-    const vector<int32_t> rows_l = has_lfile ? lookup_ref(summ_l, bim) : vector<int32_t>();
+    vector<int32_t> rows_s = lookup_ref(summ_s, bim);
+    vector<int32_t> rows_l = has_lfile ? lookup_ref(summ_l, bim) : vector<int32_t>();
     const double t_parse = walltime() - ph.t0;
     if (gpu.joinable()) gpu.join();
     g_host_threads_cap = 16;
@@ -768,6 +802,87 @@ int main(int argc, char** argv) {
     ph.put("parse_bim", t_bim);
     ph.mark("gpu_wait");      // wall time from the start to here (parse and GPU set-up overlap)
     std::cout << bim_size(bim) << " SNPs to be included from reference BIM file.\n";
+
+    // --summary: the large-effect SNPs by clumping (software/DBSLMM.R:130-184).  p = 2 pnorm(-|z|) =
+    // erfc(|z| / sqrt 2) of z = beta / se (:132-134); candidates = the summary SNPs found in the .bim
+    // with p <= pth (no allele or MAF filter here, as plink --clump; matchRef filters both lists
+    // below); priority by descending |z| (the order of ascending p without its ties at p = 0, which
+    // the R script patches over), ties by summary line; chr / bp from the reference .bim.
+    if (clump_mode) {
+        struct Cand { int32_t summ; double az, pv; };
+        vector<Cand> cand;
+        for (size_t i = 0; i < summ_s.size(); ++i) {
+            const double az = std::fabs(summ_s[i].z), pv = std::erfc(az / std::sqrt(2.0));
+            if (rows_s[i] >= 0 && pv <= p.pth) cand.push_back({static_cast<int32_t>(i), az, pv});
+        }
+        std::stable_sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) { return a.az > b.az; });
+        char pt[32];
+        snprintf(pt, sizeof(pt), "%g", p.pth);
+        if (p.dry_run) {
+            std::cout << "dry-run: " << cand.size() << " candidates at pth " << pt << "; stops before the clump\n";
+            if (p.timing) ph.print(0);
+            std::cout.flush();
+            std::_Exit(0);
+        }
+        const int32_t nc = static_cast<int32_t>(cand.size());
+        vector<int32_t> c_pos(cand.size()), c_chr(cand.size()), index_of(cand.size());
+        vector<int64_t> c_bp(cand.size());
+        std::unordered_map<string_view, int32_t> chr_code;
+        for (size_t k = 0; k < cand.size(); ++k) {
+            const int32_t r = rows_s[cand[k].summ];
+            c_pos[k] = r;
+            c_chr[k] = chr_code.emplace(bim.chr[r], static_cast<int32_t>(chr_code.size())).first->second;
+            c_bp[k] = bim.bp[r];
+        }
+        const dbslmm_clump_args ca{p.clump_r2, static_cast<int64_t>(std::llround(p.clump_kb * 1000.0))};
+        int32_t n_index = 0;
+        double clump_ms = 0.0;
+        if (dbslmm_clump(ctx, bed.p, static_cast<int64_t>(bed.n), n_ref, nc, c_pos.data(), c_chr.data(), c_bp.data(), &ca,
+                         index_of.data(), &n_index, &clump_ms) != DBSLMM_OK)
+            return fail(string("dbslmm_clump: ") + dbslmm_last_error(ctx));
+        // <eff>.clumped.txt: the index SNPs in priority order
+        vector<int32_t> absorbed(cand.size(), 0);
+        for (size_t k = 0; k < cand.size(); ++k)
+            if (index_of[k] != static_cast<int32_t>(k)) ++absorbed[index_of[k]];
+        string o = "SNP CHR BP Z P N_ABSORBED\n";
+        vector<char> is_index(summ_s.size(), 0);
+        char num[64];
+        const int prec = p.precise ? 17 : 6;
+        for (size_t k = 0; k < cand.size(); ++k) {
+            if (index_of[k] != static_cast<int32_t>(k)) continue;
+            const Summ& sm = summ_s[cand[k].summ];
+            is_index[cand[k].summ] = 1;
+            o.append(sm.snp.data(), sm.snp.size());
+            o += ' ';
+            o.append(bim.chr[c_pos[k]].data(), bim.chr[c_pos[k]].size());
+            o += ' ' + std::to_string(c_bp[k]) + ' ';
+            o.append(num, std::to_chars(num, num + sizeof(num), sm.z, std::chars_format::general, prec).ptr);
+            o += ' ';
+            o.append(num, std::to_chars(num, num + sizeof(num), cand[k].pv, std::chars_format::general, prec).ptr);
+            o += ' ' + std::to_string(absorbed[k]) + '\n';
+        }
+        {
+            std::ofstream f(p.eff + ".clumped.txt", std::ios::binary);
+            f.write(o.data(), static_cast<std::streamsize>(o.size()));
+            f.close();
+            if (!f) return fail(p.eff + ".clumped.txt cannot be written");
+        }
+        if (n_index > 0) std::cout << "Using " << pt << ", " << n_index << " SNPs are regarded as fixed effect.\n";
+        else std::cout << "Using " << pt << ", no significant SNPs.\n";
+        // the hand-off: index SNPs = the -l set, everything else the -s set, both in summary order
+        vector<Summ> all = std::move(summ_s);
+        vector<int32_t> rows_all = std::move(rows_s);
+        summ_s.clear();
+        rows_s.clear();
+        for (size_t i = 0; i < all.size(); ++i) {
+            (is_index[i] ? summ_l : summ_s).push_back(all[i]);
+            (is_index[i] ? rows_l : rows_s).push_back(rows_all[i]);
+        }
+        has_lfile = n_index > 0;
+        p.l = p.summary;
+        if (p.timing) ph.put("clump_gpu_ms", clump_ms);
+        ph.mark("clump");
+    }
 
     std::cout << "Reading summary data of small effect SNPs from [" << p.s << "]\n";
     vector<char> good_s;

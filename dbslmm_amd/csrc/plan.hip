@@ -50,6 +50,7 @@
 #include "score.hip"
 #include "trsv.hip"
 #include "pcg.hip"
+#include "clump.hip"
 
 namespace {
 // the instants of a timed run, one event each (collect_timing turns them into kernel spans)
@@ -3209,6 +3210,131 @@ int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
     for (void* q : bufs)
         if (q) (void)hipFree(q);
     return rc;
+}
+
+// dbslmm_r2_tiles over the tiles of L on the panel's image: mask mode (h_masks: kClumpMaskWords words
+// per tile; chr / bp in position order) or value mode (h_r2: n x n doubles).  pos = the bed rows in
+// position order.  Every transfer on the context's stream; complete on return.
+static int r2_tiles_run(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, const ClumpLayout& L,
+                        const std::vector<int32_t>& pos, const std::vector<int32_t>* chr,
+                        const std::vector<int64_t>* bp, double thr, int64_t window, uint32_t* h_masks,
+                        double* h_r2, double* gpu_ms) {
+    PanelImage im;
+    int32_t *d_pos = nullptr, *d_chr = nullptr;
+    int64_t* d_bp = nullptr;
+    ClumpTile* d_tiles = nullptr;
+    uint32_t* d_masks = nullptr;
+    double* d_r2 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    const int32_t n_tiles = static_cast<int32_t>(L.tiles.size());
+    const size_t mask_bytes = static_cast<size_t>(n_tiles) * kClumpMaskWords * sizeof(uint32_t);
+    const size_t r2_bytes = static_cast<size_t>(L.n) * L.n * sizeof(double);
+    int rc = DBSLMM_OK;
+    do {
+        hipError_t e;
+        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
+            (e = dev_upload(&d_pos, pos, ctx->stream)) != hipSuccess ||
+            (e = dev_upload(&d_tiles, L.tiles, ctx->stream)) != hipSuccess ||
+            (chr && (e = dev_upload(&d_chr, *chr, ctx->stream)) != hipSuccess) ||
+            (bp && (e = dev_upload(&d_bp, *bp, ctx->stream)) != hipSuccess) ||
+            (h_masks && (e = hipMalloc(&d_masks, mask_bytes)) != hipSuccess) ||
+            (h_r2 && (e = hipMalloc(&d_r2, r2_bytes)) != hipSuccess) ||
+            (e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess ||
+            (e = hipEventRecord(ev0, ctx->stream)) != hipSuccess) {
+            ctx->err = std::string("r2 tiles alloc/upload: ") + hipGetErrorString(e);
+            rc = DBSLMM_E_HIP;
+            break;
+        }
+        const int64_t kpad = im.pitch * 4;
+        const dim3 grid(static_cast<unsigned>((n_tiles + 3) / 4));
+        if (h_masks)
+            hipLaunchKernelGGL(dbslmm_r2_tiles<true>, grid, dim3(256), 0, ctx->stream, im.mem.get(), kpad, im.rows(),
+                               im.n_rows, n_ref, d_pos, L.n, d_tiles, n_tiles, d_chr, d_bp, thr, window, d_masks,
+                               static_cast<double*>(nullptr));
+        else
+            hipLaunchKernelGGL(dbslmm_r2_tiles<false>, grid, dim3(256), 0, ctx->stream, im.mem.get(), kpad, im.rows(),
+                               im.n_rows, n_ref, d_pos, L.n, d_tiles, n_tiles, static_cast<const int32_t*>(nullptr),
+                               static_cast<const int64_t*>(nullptr), 0.0, int64_t(0), static_cast<uint32_t*>(nullptr),
+                               d_r2);
+        float ms = 0.0f;
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev1, ctx->stream)) != hipSuccess ||
+            (h_masks && (e = hipMemcpyAsync(h_masks, d_masks, mask_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
+            (h_r2 && (e = hipMemcpyAsync(h_r2, d_r2, r2_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
+            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) {
+            ctx->err = std::string("r2 tiles run: ") + hipGetErrorString(e);
+            rc = DBSLMM_E_HIP;
+            break;
+        }
+        if (gpu_ms) *gpu_ms = ms;
+    } while (0);
+    void* bufs[] = {d_pos, d_chr, d_bp, d_tiles, d_masks, d_r2};
+    for (void* q : bufs)
+        if (q) (void)hipFree(q);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    return rc;
+}
+
+// the row-list checks shared by dbslmm_ld_r2 and dbslmm_clump
+static int r2_rows_check(dbslmm_ctx* ctx, int64_t bed_len, int32_t n_ref, const int32_t* pos, int32_t n_rows) {
+    ARG_CHECK(ctx, 9 * round_up(n_ref, gram::kKpadAlign) < (int64_t(1) << 24),
+              "n_ref past the FP4 Gram's exact range (9 * roundup(n_ref, 256) < 2^24)");
+    const int64_t bps = bed_row_bytes(n_ref);
+    for (int32_t j = 0; j < n_rows; ++j)
+        ARG_CHECK(ctx, pos[j] >= 0 && 3 + (static_cast<int64_t>(pos[j]) + 1) * bps <= bed_len, "row out of range");
+    return DBSLMM_OK;
+}
+
+// LD r2 of every pair of the listed rows (clump.hip, value mode).
+int dbslmm_ld_r2(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, const int32_t* pos,
+                 int32_t n_rows, double* r2) {
+    if (!ctx) return DBSLMM_E_ARG;
+    ON_FIRST_DEVICE(ctx, dbslmm_ld_r2(ctx0_, bed, bed_len, n_ref, pos, n_rows, r2));
+    ARG_CHECK(ctx, bed && n_ref > 1 && n_rows >= 0 && n_rows <= 8192 && (n_rows == 0 || (pos && r2)), "bad arguments");
+    if (const int rc = r2_rows_check(ctx, bed_len, n_ref, pos, n_rows)) return rc;
+    if (n_rows == 0) return DBSLMM_OK;
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const ClumpLayout L = build_dense_layout(n_rows);
+    return r2_tiles_run(ctx, bed, bed_len, n_ref, L, std::vector<int32_t>(pos, pos + n_rows), nullptr, nullptr, 0.0, 0,
+                        nullptr, r2, nullptr);
+}
+
+// Clumping (software/DBSLMM.R:139-145, `plink --clump`): the index SNPs of the candidates.
+int dbslmm_clump(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_cand,
+                 const int32_t* pos, const int32_t* chr, const int64_t* bp, const dbslmm_clump_args* args,
+                 int32_t* index_of, int32_t* n_index, double* gpu_ms) {
+    if (!ctx) return DBSLMM_E_ARG;
+    ON_FIRST_DEVICE(ctx, dbslmm_clump(ctx0_, bed, bed_len, n_ref, n_cand, pos, chr, bp, args, index_of, n_index, gpu_ms));
+    ARG_CHECK(ctx, bed && args && n_ref > 1 && n_cand >= 0 && (n_cand == 0 || (pos && chr && bp && index_of)),
+              "bad arguments");
+    ARG_CHECK(ctx, args->r2 > 0.0 && args->r2 <= 1.0, "clump r2 threshold outside (0, 1]");
+    ARG_CHECK(ctx, args->window_bp >= 0, "clump window below 0");
+    if (const int rc = r2_rows_check(ctx, bed_len, n_ref, pos, n_cand)) return rc;
+    if (n_index) *n_index = 0;
+    if (gpu_ms) *gpu_ms = 0.0;
+    if (n_cand == 0) return DBSLMM_OK;
+    ClumpLayout L = build_clump_layout(n_cand, chr, bp, args->window_bp);
+    clump_index_columns(L);
+    std::vector<uint32_t> masks(L.tiles.size() * kClumpMaskWords);
+    if (!L.tiles.empty()) {
+        KEY_CHECK(ctx, bed, bed_len, n_ref);
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::vector<int32_t> spos(static_cast<size_t>(n_cand)), schr(static_cast<size_t>(n_cand));
+        std::vector<int64_t> sbp(static_cast<size_t>(n_cand));
+        for (int32_t p = 0; p < n_cand; ++p) {
+            const int32_t k = L.order[static_cast<size_t>(p)];
+            spos[static_cast<size_t>(p)] = pos[k];
+            schr[static_cast<size_t>(p)] = chr[k];
+            sbp[static_cast<size_t>(p)] = bp[k];
+        }
+        if (const int rc = r2_tiles_run(ctx, bed, bed_len, n_ref, L, spos, &schr, &sbp, args->r2, args->window_bp,
+                                        masks.data(), nullptr, gpu_ms))
+            return rc;
+    }
+    const int32_t ni = clump_greedy(L, masks.data(), index_of);
+    if (n_index) *n_index = ni;
+    return DBSLMM_OK;
 }
 
 #ifdef DBSLMM_STAMPS

@@ -12,6 +12,8 @@
  *                         repeated with inputs resident in HBM (bench, h2f tuning).
  *   dbslmm_bed_maf        the MAF pass of IO::readBim (dtpr.cpp:93-102) = readSNPIm over every
  *                         reference SNP, maf only.
+ *   dbslmm_clump          the large-effect clumping of software/DBSLMM.R:139-145 (`plink --clump` on
+ *                         the reference panel): the index SNPs of a candidate list.
  *   dbslmm_read_snp_std   IO::readSNPIm + SNPPROC::nomalizeVec (dtpr.cpp:285-364, 375-380) for a
  *                         list of bed rows: standardised fp64 columns (parity / diagnostics).
  *
@@ -31,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 19
+#define DBSLMM_ABI_VERSION 20
 
 enum {
     DBSLMM_OK = 0,
@@ -486,6 +488,41 @@ int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t
  * is its key, else an upload of its own); a multi-device context answers from its first device. */
 int dbslmm_bed_row_stats(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
                          int64_t n_rows, int32_t* out /* n_rows x 3: sum, sumsq, nmiss */);
+
+/* LD r2 between rows of the reference panel (ABI 20; clump.hip).  r_ij is the Pearson correlation
+ * of the dosages of bed rows i and j over the n_ref individuals, missing calls at the row mean
+ * (readSNPIm's convention; the correlation of the standardised columns dbslmm_read_snp_std returns).
+ * Pairs of rows without a missing call are computed from exact integers: r2 = N^2 / (D_i D_j) with
+ * N = n G_ij - S_i S_j and D_i = n sq_i - S_i^2 formed in int64 and three fp64 roundings.  A row
+ * without variance or without an observed call has r2 = NaN with every row, itself included.
+ * Both entries follow the panel-key rules of dbslmm_bed_maf (the context's cached image when
+ * (bed, bed_len) is its key, else an upload of their own); a multi-device context answers from its
+ * first device.  DBSLMM_E_ARG for a pos outside the panel or n_ref past the FP4 Gram's exact range
+ * (9 * roundup(n_ref, 256) < 2^24: n_ref <= 1 863 936).
+ *
+ * r2 of every pair of bed rows pos[0..n_rows): n_rows x n_rows fp64, row-major, symmetric; NaN in
+ * the row and column of a row without variance or observed call.  n_rows <= 8192. */
+int dbslmm_ld_r2(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
+                 const int32_t* pos, int32_t n_rows, double* r2);
+
+/* Clumping: PLINK's greedy rule (`--clump-p1` candidates only; DBSLMM uses nothing but the index
+ * SNPs, which `--clump-p2` cannot change).  The candidates -- bed row pos[k], chromosome code chr[k]
+ * (any integer per chromosome), base pair bp[k] -- come in priority order, most significant first.
+ * Walking them in that order, a candidate not yet absorbed becomes an index SNP and absorbs every
+ * not yet absorbed candidate j on its chromosome with |bp_j - bp_k| <= window_bp and r2_kj >= r2.
+ * Absorption is not transitive: if A absorbs B and C is linked only to B, C becomes an index SNP of
+ * its own.  NaN compares false: a row without variance or observed call neither absorbs nor is
+ * absorbed.  r2 is the dosage correlation above, not PLINK's haplotype-frequency estimate, and PLINK
+ * documents neither its treatment of r2 exactly at the threshold nor of p-value ties: the index set
+ * is this rule's, not a replay of a PLINK run.
+ * r2 in (0, 1], window_bp >= 0, else DBSLMM_E_ARG. */
+typedef struct dbslmm_clump_args { double r2; int64_t window_bp; } dbslmm_clump_args;
+/* Candidates in priority order (most significant first).  index_of[k] = the candidate that
+ * absorbed k (k itself for an index SNP); n_index (optional); gpu_ms (optional) = event time of
+ * the tile kernel.  n_cand == 0 is valid.  Rows may repeat (a repeat has r2 = 1 with its twin). */
+int dbslmm_clump(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_cand,
+                 const int32_t* pos, const int32_t* chr, const int64_t* bp,
+                 const dbslmm_clump_args* args, int32_t* index_of, int32_t* n_index, double* gpu_ms);
 
 /* readSNPIm + nomalizeVec for rows pos[0..n_rows): out is n_ref x n_rows column-major fp64
  * (column j = standardised dosages of bed row pos[j]); maf (optional) n_rows entries. */
