@@ -804,7 +804,7 @@ static int mp_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_sc
 // image starting at bed + r0 * bps: its first 3 bytes stand in for the magic (never read) and row
 // r0 is its row 0, so no copy is needed.
 static int mp_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int32_t n_ref, int64_t n_snp, double* maf) {
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
+    const int64_t bps = bed_row_bytes(n_ref);
     const int G = static_cast<int>(ctx->subs.size());
     std::vector<int> rc(G, DBSLMM_OK);
     std::vector<std::thread> th;

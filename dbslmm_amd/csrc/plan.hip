@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/dbslmm_hip.h"
+#include "dev_bufs.hpp"
 #include "out_ranges.hpp"
 #include "plan_layout.hpp"
 
@@ -166,6 +167,7 @@ struct dbslmm_plan : PlanLayout::Kept {
     double sigma_s = 0.0, tau = 0.8;
     int64_t bed_len = 0;
     // device
+    DevBufs bufs;                      // owns every d_* member below (freed with the plan)
     PanelImage img;                    // own upload, or the context's cached image (shared)
     const uint8_t* d_img = nullptr;    // img.mem.get(): pitch kpad / 4, zero-dosage row img.n_rows
     int32_t *d_slot_pos = nullptr, *d_slot_block = nullptr, *d_slot_out = nullptr;
@@ -306,7 +308,7 @@ struct dbslmm_plan : PlanLayout::Kept {
     do {                                                                                 \
         hipError_t e_ = (expr);                                                          \
         if (e_ != hipSuccess) {                                                          \
-            (ctx)->err = std::string(#expr) + " (plan.hip:" + std::to_string(__LINE__) + "): " + \
+            (ctx)->err = std::string(#expr) + " (" __FILE_NAME__ ":" + std::to_string(__LINE__) + "): " + \
                          hipGetErrorString(e_);                                          \
             return DBSLMM_E_HIP;                                                         \
         }                                                                                \
@@ -552,7 +554,7 @@ static std::shared_ptr<uint8_t> dev_shared(uint8_t* d, int dev) {
 // individuals; complete on return.
 static hipError_t image_from_verbatim(dbslmm_ctx* ctx, const uint8_t* d_bed, int64_t bed_len, int32_t n_ref,
                                       PanelImage* out) {
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
+    const int64_t bps = bed_row_bytes(n_ref);
     const int64_t n_rows = (bed_len - 3) / bps;
     if (n_rows >= INT32_MAX) return hipErrorInvalidValue;
     const int64_t pitch = round_up(n_ref, gram::kKpadAlign) / 4;
@@ -592,25 +594,12 @@ static hipError_t panel_image(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_l
         // (cached for another n_ref and the verbatim bytes are gone: upload again below -- a host
         // array; the entry points turn a file-descriptor key away before this, KEY_CHECK)
     }
+    DevBufs B(ctx->device);   // the verbatim upload lives until the image is made
     uint8_t* d_bed = nullptr;
-    hipError_t e = hipMalloc(&d_bed, bed_len + kBedPad);
+    hipError_t e = B.alloc(&d_bed, bed_len + kBedPad);
     if (e != hipSuccess) return e;
     if ((e = bed_to_device(ctx, d_bed, bed, bed_len)) == hipSuccess) e = image_from_verbatim(ctx, d_bed, bed_len, n_ref, out);
-    (void)hipFree(d_bed);
     return e;
-}
-
-// Allocate and fill a device array on stream st; complete on return.  Every host -> device copy
-// of the library is ordered on the stream its consumers run on (or one they are forked from):
-// null-stream transfers are not ordered against the contexts' non-blocking streams, and a pageable
-// hipMemcpy may return before its DMA has landed.
-template <typename T>
-static hipError_t dev_upload(T** dst, const std::vector<T>& src, hipStream_t st) {
-    size_t bytes = std::max<size_t>(sizeof(T), src.size() * sizeof(T));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), bytes);
-    if (e != hipSuccess || src.empty()) return e;
-    e = hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 
 template <int NR>
@@ -699,11 +688,11 @@ int dbslmm_ctx_create(int device, dbslmm_ctx** out) {
             set_trsv_lds<1>() == hipSuccess && set_trsv_lds<2>() == hipSuccess;
         // The first kernel launch of the process loads the library's code object (~30 ms on the
         // box): done here, beside the caller's .bed upload, instead of inside its first MAF pass
+        DevBufs B(device);
         double* d_warm = nullptr;
-        if (c->setup_ok && hipMalloc(&d_warm, sizeof(double)) == hipSuccess) {
+        if (c->setup_ok && B.alloc(&d_warm, 1) == hipSuccess) {
             hipLaunchKernelGGL(dbslmm_set_scalar, dim3(1), dim3(1), 0, c->stream2, d_warm, 0.0);
             c->setup_ok = hipStreamSynchronize(c->stream2) == hipSuccess;
-            (void)hipFree(d_warm);
         }
     });
     *out = c;
@@ -796,23 +785,6 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
     if (p->h_mflag) (void)hipHostFree(p->h_mflag);
     if (p->so_ev) (void)hipEventDestroy(p->so_ev);
     p->img = PanelImage{};                      // (shared with the context when it came from its cache)
-    void* bufs[] = {p->d_slot_pos, p->d_slot_block, p->d_slot_out, p->d_z,
-                    p->d_S, p->d_mu, p->d_rsd, p->d_y, p->d_flags, p->d_status, p->d_order,
-                    p->d_blk_id, p->d_row0, p->d_m, p->d_ms, p->d_ld, p->d_matoff, p->d_tiles,
-                    p->d_M, p->d_beta_s, p->d_beta_l, p->d_tlist, p->d_btiles, p->d_htiles, p->d_dshift,
-                    p->d_tlist_multi, p->d_tri_f, p->d_tri_b, p->d_foff, p->d_tflags, p->d_tb,
-                    p->d_cheb, p->d_coef, p->d_stamps, p->d_tepi, p->d_cheb_items,
-                    p->d_tcheb_blocks, p->d_cgrec, p->d_cgconv, p->d_cgit, p->d_G16, p->d_pblk,
-                    p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
-                    p->d_pitb, p->d_pdone, p->d_pact, p->d_off16, p->d_ld16, p->d_pflist, p->d_pfnext, p->d_pfin};
-    for (void* b : bufs)
-        if (b) {
-            const hipError_t e = hipFree(b);
-#ifdef DBSLMM_DIAG
-            if (e != hipSuccess) fprintf(stderr, "plan_destroy: hipFree(%p) -> %s\n", b, hipGetErrorString(e));
-#endif
-            (void)e;
-        }
     for (hipEvent_t e : p->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->dl_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->tev) (void)hipEventDestroy(e);
@@ -823,7 +795,7 @@ void dbslmm_plan_destroy(dbslmm_plan* p) {
         if (g) (void)hipGraphExecDestroy(g);
     for (hipGraphExec_t g : p->graph_rest)
         if (g) (void)hipGraphExecDestroy(g);
-    delete p;
+    delete p;                                   // (its DevBufs frees the device buffers)
 }
 
 int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** out) {
@@ -850,6 +822,7 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     auto* p = new dbslmm_plan();
     static_cast<PlanLayout::Kept&>(*p) = std::move(L.keep);
     p->ctx = ctx;
+    p->bufs.device = ctx->device;
     p->n_ref = pr->n_ref;
     p->n_obs = pr->n_obs;
     p->num_block = pr->num_block;
@@ -884,41 +857,37 @@ int dbslmm_plan_create(dbslmm_ctx* ctx, const dbslmm_problem* pr, dbslmm_plan** 
     // (every memset of the plan's buffers is ordered on the main stream, which every run starts
     // on: a null-stream hipMemset is not ordered against the context's non-blocking streams, and
     // one still running under the first run's Gram would zero matrix entries behind it)
-    if ((e = dev_upload(&p->d_slot_pos, L.slot_pos, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_slot_block, L.slot_block, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_slot_out, p->h_slot_out, ctx->stream)) != hipSuccess) return fail("upload slots");
-    if ((e = dev_upload(&p->d_z, L.z, ctx->stream)) != hipSuccess) return fail("upload z");
-    if ((e = dev_upload(&p->d_row0, p->h_row0, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_m, p->h_m, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_ms, p->h_ms, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_ld, p->h_ld, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_matoff, p->h_matoff, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_blk_id, p->h_blk_id, ctx->stream)) != hipSuccess) return fail("upload blocks");
-    if ((e = dev_upload(&p->d_order, L.order, ctx->stream)) != hipSuccess) return fail("upload order");
-    if ((e = dev_upload(&p->d_tiles, L.tiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_btiles, L.btiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_htiles, L.htiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
-    if ((e = dev_upload(&p->d_tlist, L.tlist, ctx->stream)) != hipSuccess) return fail("upload tiled lists");
-    if ((e = dev_upload(&p->d_tri_f, L.tri_f, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if ((e = dev_upload(&p->d_tri_b, L.tri_b, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if ((e = dev_upload(&p->d_foff, L.foff, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if ((e = dev_upload(&p->d_tb, p->h_tb, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
-    if (!L.tcheb_list.empty() && (e = dev_upload(&p->d_tcheb_blocks, L.tcheb_list, ctx->stream)) != hipSuccess)
+    if ((e = p->bufs.upload(&p->d_slot_pos, L.slot_pos, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = p->bufs.upload(&p->d_slot_block, L.slot_block, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = p->bufs.upload(&p->d_slot_out, p->h_slot_out, ctx->stream)) != hipSuccess) return fail("upload slots");
+    if ((e = p->bufs.upload(&p->d_z, L.z, ctx->stream)) != hipSuccess) return fail("upload z");
+    if ((e = p->bufs.upload(&p->d_row0, p->h_row0, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_m, p->h_m, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_ms, p->h_ms, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_ld, p->h_ld, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_matoff, p->h_matoff, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_blk_id, p->h_blk_id, ctx->stream)) != hipSuccess) return fail("upload blocks");
+    if ((e = p->bufs.upload(&p->d_order, L.order, ctx->stream)) != hipSuccess) return fail("upload order");
+    if ((e = p->bufs.upload(&p->d_tiles, L.tiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = p->bufs.upload(&p->d_btiles, L.btiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = p->bufs.upload(&p->d_htiles, L.htiles, ctx->stream)) != hipSuccess) return fail("upload tiles");
+    if ((e = p->bufs.upload(&p->d_tlist, L.tlist, ctx->stream)) != hipSuccess) return fail("upload tiled lists");
+    if ((e = p->bufs.upload(&p->d_tri_f, L.tri_f, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = p->bufs.upload(&p->d_tri_b, L.tri_b, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = p->bufs.upload(&p->d_foff, L.foff, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if ((e = p->bufs.upload(&p->d_tb, p->h_tb, ctx->stream)) != hipSuccess) return fail("upload trsv lists");
+    if (!L.tcheb_list.empty() && (e = p->bufs.upload(&p->d_tcheb_blocks, L.tcheb_list, ctx->stream)) != hipSuccess)
         return fail("upload trsv lists");
     // [tile flags | ticket counter | error word | spare]
-    if ((e = hipMalloc(&p->d_tflags, (p->n_tflags + 3) * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc trsv flags");
-    if ((e = hipMemsetAsync(p->d_tflags, 0, (p->n_tflags + 3) * sizeof(int32_t), ctx->stream)) != hipSuccess) return fail("hipMemset trsv flags");
-    if ((e = hipMalloc(&p->d_tepi, std::max(1, p->n_tflags) * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc trsv flags");
-    if ((e = hipMemsetAsync(p->d_tepi, 0, std::max(1, p->n_tflags) * sizeof(int32_t), ctx->stream)) != hipSuccess) return fail("hipMemset trsv flags");
-    const size_t ns = std::max<size_t>(1, p->n_slots);
-    if ((e = hipMalloc(&p->d_S, ns * sizeof(double))) != hipSuccess) return fail("hipMalloc stats");
-    if ((e = hipMalloc(&p->d_mu, ns * sizeof(double))) != hipSuccess) return fail("hipMalloc stats");
-    if ((e = hipMalloc(&p->d_rsd, ns * sizeof(double))) != hipSuccess) return fail("hipMalloc stats");
+    if ((e = p->bufs.zeroed(&p->d_tflags, p->n_tflags + 3, ctx->stream)) != hipSuccess) return fail("hipMalloc trsv flags");
+    if ((e = p->bufs.zeroed(&p->d_tepi, p->n_tflags, ctx->stream)) != hipSuccess) return fail("hipMalloc trsv flags");
+    if ((e = p->bufs.alloc(&p->d_S, p->n_slots)) != hipSuccess) return fail("hipMalloc stats");
+    if ((e = p->bufs.alloc(&p->d_mu, p->n_slots)) != hipSuccess) return fail("hipMalloc stats");
+    if ((e = p->bufs.alloc(&p->d_rsd, p->n_slots)) != hipSuccess) return fail("hipMalloc stats");
     const size_t nbk = std::max<int32_t>(1, std::max(p->n_nonempty, p->num_block));
     p->nbk = static_cast<int64_t>(nbk);
-    if ((e = hipMalloc(&p->d_flags, nbk * sizeof(int32_t))) != hipSuccess) return fail("hipMalloc flags");
     // (zeroed here for the PCG route, whose front kernel only sets bits: run_pcg)
-    if ((e = hipMemsetAsync(p->d_flags, 0, nbk * sizeof(int32_t), ctx->stream)) != hipSuccess) return fail("hipMemset flags");
+    if ((e = p->bufs.zeroed(&p->d_flags, nbk, ctx->stream)) != hipSuccess) return fail("hipMalloc flags");
     // (the block matrices, betas, status and sigma scalars are allocated by the first run, for as
     // many factorisation copies as it solves: ensure_copies -- an h2f plan is not sized twice)
     if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail("plan set-up");
@@ -1052,20 +1021,16 @@ static int ensure_copies(dbslmm_plan* p, int n, int mc) {
     mc = std::max(mc, p->m_copies);
     std::lock_guard<std::mutex> lk(g_capture_mu);   // device-wide sync + synchronous memset
     HIP_TRY(ctx, hipDeviceSynchronize());
-    void* old[] = {p->d_M, p->d_dshift, p->d_y, p->d_beta_s, p->d_beta_l, p->d_status};
-    for (void* q : old)
-        if (q) (void)hipFree(q);
-    p->d_M = p->d_dshift = p->d_y = p->d_beta_s = p->d_beta_l = nullptr;
-    p->d_status = nullptr;
+    DevBufs& B = p->bufs;
+    B.release_all(p->d_M, p->d_dshift, p->d_y, p->d_beta_s, p->d_beta_l, p->d_status);
     const size_t nn = static_cast<size_t>(n), nm = static_cast<size_t>(mc);
     // (+ 256 elements: the PCG product's masked row segments may run past the last block's rows)
-    HIP_TRY(ctx, hipMalloc(&p->d_M, (std::max<size_t>(1, nm * p->M_elems) + 256) * sizeof(double)));
-    HIP_TRY(ctx, hipMemsetAsync(p->d_M, 0, (std::max<size_t>(1, nm * p->M_elems) + 256) * sizeof(double), ctx->stream));
-    HIP_TRY(ctx, hipMalloc(&p->d_dshift, nn * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_y, nn * std::max<int64_t>(1, p->n_slots) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_beta_s, nn * std::max<int64_t>(1, p->n_s) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_beta_l, nn * std::max<int64_t>(1, p->n_l) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_status, nn * p->nbk * sizeof(int32_t)));
+    HIP_TRY(ctx, B.zeroed(&p->d_M, std::max<size_t>(1, nm * p->M_elems) + 256, ctx->stream));
+    HIP_TRY(ctx, B.alloc(&p->d_dshift, nn));
+    HIP_TRY(ctx, B.alloc(&p->d_y, nn * std::max<int64_t>(1, p->n_slots)));
+    HIP_TRY(ctx, B.alloc(&p->d_beta_s, nn * std::max<int64_t>(1, p->n_s)));
+    HIP_TRY(ctx, B.alloc(&p->d_beta_l, nn * std::max<int64_t>(1, p->n_l)));
+    HIP_TRY(ctx, B.alloc(&p->d_status, nn * p->nbk));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     p->n_copies = n;
     p->m_copies = mc;
@@ -1134,7 +1099,7 @@ static int run_pbwd(dbslmm_plan* p, double isn, int copy, const TGroup& grp) {
     const int64_t vs = std::max<int64_t>(1, p->n_slots);
     if (!p->d_cheb) {
         std::lock_guard<std::mutex> lk(g_capture_mu);
-        HIP_TRY(ctx, hipMalloc(&p->d_cheb, 6 * trsv::kMaxR * vs * sizeof(double)));
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_cheb, 6 * trsv::kMaxR * vs));
     }
     const int64_t c = copy;
     trsv::Args a{};
@@ -1314,14 +1279,14 @@ static int cheb_prepare(dbslmm_plan* p, const ChebPlan& cp, hipStream_t st) {
     const int64_t vs = std::max<int64_t>(1, p->n_slots);
     if (!p->d_cheb) {
         std::lock_guard<std::mutex> lk(g_capture_mu);
-        HIP_TRY(ctx, hipMalloc(&p->d_cheb, 6 * trsv::kMaxR * vs * sizeof(double)));
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_cheb, 6 * trsv::kMaxR * vs));
     }
     if (p->h2f_cg && !p->d_cgconv) {
         std::lock_guard<std::mutex> lk(g_capture_mu);
         const size_t nb = std::max(1, p->n_nonempty);
-        HIP_TRY(ctx, hipMalloc(&p->d_cgrec, nb * trsv::kMaxR * 2 * sizeof(double)));
-        HIP_TRY(ctx, hipMalloc(&p->d_cgconv, nb * sizeof(int32_t)));
-        HIP_TRY(ctx, hipMalloc(&p->d_cgit, nb * sizeof(int32_t)));
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_cgrec, nb * trsv::kMaxR * 2));
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_cgconv, nb));
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_cgit, nb));
     }
     // every block's CG pass count starts at 0 each run (the rest group of sub_split = 2 iterates by
     // Chebyshev and never writes it; workload[16] sums it over every tiled block: ADVICE r05)
@@ -1334,9 +1299,8 @@ static int cheb_prepare(dbslmm_plan* p, const ChebPlan& cp, hipStream_t st) {
     HIP_TRY(ctx, hipStreamSynchronize(st));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
     if (p->coef_cap < static_cast<int32_t>(cp.coef.size())) {
-        if (p->d_coef) (void)hipFree(p->d_coef);
-        p->d_coef = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p->d_coef, cp.coef.size() * sizeof(double)));
+        (void)p->bufs.release(p->d_coef);
+        HIP_TRY(ctx, p->bufs.alloc(&p->d_coef, cp.coef.size()));
         p->coef_cap = static_cast<int32_t>(cp.coef.size());
     }
     HIP_TRY(ctx, hipMemcpyAsync(p->d_coef, cp.coef.data(), cp.coef.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1409,9 +1373,8 @@ static int run_cheb(dbslmm_plan* p, double isn, const ChebPlan& cp, const TGroup
             std::vector<int32_t> items;
             build_cheb_items(p, K, items);
             HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (p->d_cheb_items) (void)hipFree(p->d_cheb_items);
-            p->d_cheb_items = nullptr;
-            HIP_TRY(ctx, dev_upload(&p->d_cheb_items, items, ctx->stream));
+            (void)p->bufs.release(p->d_cheb_items);
+            HIP_TRY(ctx, p->bufs.upload(&p->d_cheb_items, items, ctx->stream));
             p->n_cheb_items = static_cast<int32_t>(items.size() / 2);
             p->cheb_items_K = K;
         }
@@ -1455,7 +1418,7 @@ static int run_cheb(dbslmm_plan* p, double isn, const ChebPlan& cp, const TGroup
         if (getenv("DBSLMM_TRSV_STAMPS")) {
             int bmax = p->h_tb[0];
             for (int32_t b : p->h_tb) if (p->h_m[b] > p->h_m[bmax]) bmax = b;
-            if (!p->d_stamps) HIP_TRY(ctx, hipMalloc(&p->d_stamps, 8 * 4096 * sizeof(unsigned long long)));
+            if (!p->d_stamps) HIP_TRY(ctx, p->bufs.alloc(&p->d_stamps, 8 * 4096));
             a.stamps = p->d_stamps;
             a.stamp_b = bmax;
         }
@@ -1624,21 +1587,21 @@ static int pcg_layout(dbslmm_plan* p, int n) {
             o += l * l;
         }
         const size_t e = static_cast<size_t>(o) + 256;
-        HIP_TRY(ctx, hipMalloc(&p->d_G16, e * sizeof(uint16_t)));
-        HIP_TRY(ctx, hipMemsetAsync(p->d_G16, 0, e * sizeof(uint16_t), ctx->stream));
-        HIP_TRY(ctx, dev_upload(&p->d_off16, off, ctx->stream));
-        HIP_TRY(ctx, dev_upload(&p->d_ld16, ldv, ctx->stream));
+        HIP_TRY(ctx, p->bufs.zeroed(&p->d_G16, e, ctx->stream));
+        HIP_TRY(ctx, p->bufs.upload(&p->d_off16, off, ctx->stream));
+        HIP_TRY(ctx, p->bufs.upload(&p->d_ld16, ldv, ctx->stream));
         p->h_off16 = off;
     }
     if (!p->h_pmon) HIP_TRY(ctx, hipHostMalloc(&p->h_pmon, (1 + std::max(1, p->n_nonempty)) * sizeof(int32_t),
                                                hipHostMallocDefault));
     if (p->pcg_n == n) return DBSLMM_OK;
-    void* old[] = {p->d_pblk, p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
-                   p->d_pitb, p->d_pdone, p->d_pact, p->d_pflist, p->d_pfin};
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* q : old)
-        if (q) (void)hipFree(q);
-    p->d_pflist = nullptr;               // (uploaded below only when some block is solved whole)
+    // the old layout's buffers go, each member null from here on: a failure below leaves nothing dangling
+    // (d_pflist is uploaded again only when some block is solved whole)
+    DevBufs& B = p->bufs;
+    B.release_all(p->d_pblk, p->d_pitem, p->d_prow, p->d_pvec, p->d_ppart, p->d_pdot, p->d_pqs, p->d_pcnv,
+                  p->d_pitb, p->d_pdone, p->d_pact, p->d_pflist, p->d_pfin);
+    p->pcg_n = 0;                        // (no layout until the new one is complete)
     p->pcg_trim = false;                 // (until a run of this layout has read the flags)
     using namespace pcg;
     std::vector<PcgBlk> blk;
@@ -1712,8 +1675,8 @@ static int pcg_layout(dbslmm_plan* p, int n) {
     for (int b = 0; b < static_cast<int>(blk.size()); ++b)
         if (!blk[b].fused)
             for (int c = 0; c < n; ++c) p->h_pfpairs.push_back(int2{b, c});
-    if (!flist.empty()) HIP_TRY(ctx, dev_upload(&p->d_pflist, flist, ctx->stream));
-    if (!flist.empty() && !p->d_pfnext) HIP_TRY(ctx, hipMalloc(&p->d_pfnext, 16));
+    if (!flist.empty()) HIP_TRY(ctx, B.upload(&p->d_pflist, flist, ctx->stream));
+    if (!flist.empty() && !p->d_pfnext) HIP_TRY(ctx, B.alloc(&p->d_pfnext, 4));   // (16 B)
     p->n_pblk = static_cast<int32_t>(blk.size());
     p->n_pitem = static_cast<int32_t>(items.size());
     p->n_prow = static_cast<int32_t>(rows.size());
@@ -1725,18 +1688,18 @@ static int pcg_layout(dbslmm_plan* p, int n) {
     p->pcg_vstride = vo;
     p->h_pmat = mat;
     p->h_ppart = part;
-    HIP_TRY(ctx, dev_upload(&p->d_pblk, blk, ctx->stream));
-    HIP_TRY(ctx, dev_upload(&p->d_pitem, items, ctx->stream));
-    HIP_TRY(ctx, dev_upload(&p->d_prow, rows, ctx->stream));
-    HIP_TRY(ctx, hipMalloc(&p->d_pvec, std::max<int64_t>(1, 6 * n * vo) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_ppart, std::max<int64_t>(1, po) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pdot, std::max<int64_t>(1, dof) * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pqs, std::max<int32_t>(1, sco) * pcg::kQS * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pcnv, std::max<int32_t>(1, sco) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pitb, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pdone, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pact, sizeof(int32_t)));
-    HIP_TRY(ctx, hipMalloc(&p->d_pfin, std::max<int32_t>(1, p->n_pblk) * sizeof(int32_t)));
+    HIP_TRY(ctx, B.upload(&p->d_pblk, blk, ctx->stream));
+    HIP_TRY(ctx, B.upload(&p->d_pitem, items, ctx->stream));
+    HIP_TRY(ctx, B.upload(&p->d_prow, rows, ctx->stream));
+    HIP_TRY(ctx, B.alloc(&p->d_pvec, 6 * n * vo));
+    HIP_TRY(ctx, B.alloc(&p->d_ppart, po));
+    HIP_TRY(ctx, B.alloc(&p->d_pdot, dof));
+    HIP_TRY(ctx, B.alloc(&p->d_pqs, static_cast<size_t>(std::max<int32_t>(1, sco)) * pcg::kQS));
+    HIP_TRY(ctx, B.alloc(&p->d_pcnv, sco));
+    HIP_TRY(ctx, B.alloc(&p->d_pitb, p->n_pblk));
+    HIP_TRY(ctx, B.alloc(&p->d_pdone, p->n_pblk));
+    HIP_TRY(ctx, B.alloc(&p->d_pact, 1));
+    HIP_TRY(ctx, B.alloc(&p->d_pfin, p->n_pblk));
     p->pcg_n = n;
     return DBSLMM_OK;
 }
@@ -2106,9 +2069,8 @@ static int run_impl(dbslmm_plan* p, const double* sigmas, int n) {
             std::vector<int32_t> tlist;
             p->tl_multi.clear();
             build_tiled(p->h_m, p->h_tb, n, p->n_nonempty, p->tl_multi, tlist);
-            if (p->d_tlist_multi) (void)hipFree(p->d_tlist_multi);
-            p->d_tlist_multi = nullptr;
-            HIP_TRY(ctx, dev_upload(&p->d_tlist_multi, tlist, ctx->stream));
+            (void)p->bufs.release(p->d_tlist_multi);
+            HIP_TRY(ctx, p->bufs.upload(&p->d_tlist_multi, tlist, ctx->stream));
             if (p->graph_multi) (void)hipGraphExecDestroy(p->graph_multi);
             p->graph_multi = nullptr;
             p->multi_n = n;
@@ -2703,639 +2665,7 @@ int dbslmm_est(dbslmm_ctx* ctx, const dbslmm_problem* pr, double* beta_s, double
     return rc;
 }
 
-// The last h2f run iterated the last sigma's tiled blocks on another copy's factor and wrote no
-// matrix for them: re-run that sigma alone (Gram + factorisation) so the variance has its factor.
-// A multi-device plan does this for every shard (and waits) before any shard's variance starts,
-// so no shard captures a graph while another runs the variance's synchronous calls.
-static int variance_factor(dbslmm_plan* p) {
-    if (const int rc = pcg_finish(p)) return rc;
-    if (!p->cheb_pending_var && !p->pcg_pending_var) return DBSLMM_OK;
-    const double sg = p->sigma_run;
-    p->cheb_pending_var = false;
-    p->pcg_pending_var = false;
-    p->force_factor = true;          // the variance needs the factor of this sigma
-    const int rc = run_impl(p, &sg, 1);
-    p->force_factor = false;
-    return rc;
-}
-
-// Test-set variance: compact the test panel to the plan's slots and the
-// indicator-1 individuals, standardise (readSNPIm + nomalizeVec over n_test), then one
-// forward-substitution pass per block against the factor the solve left in d_M.
-int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* diags,
-                         int32_t* n_test_out) {
-    if (!p) return DBSLMM_E_ARG;
-    dbslmm_ctx* ctx = p->ctx;
-    if (!p->ran) { ctx->err = "plan_variance before plan_run"; return DBSLMM_E_STATE; }
-    if (p->stopped) { ctx->err = "plan_variance after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
-    if (p->mp) return mp_variance(p, tp, diags, n_test_out);
-    ARG_CHECK(ctx, tp && tp->bed && tp->indicator && tp->n_total > 0, "bad test panel");
-    if (const int rc = variance_factor(p)) return rc;
-    ARG_CHECK(ctx, p->n_s == 0 || tp->s_pos, "test panel s_pos missing");
-    ARG_CHECK(ctx, p->n_l == 0 || tp->l_pos, "test panel l_pos missing");
-    std::vector<int32_t> sel;
-    for (int32_t i = 0; i < tp->n_total; ++i)
-        if (tp->indicator[i] != 0) sel.push_back(i);   // readSNPIm skips only 0 entries
-    const int32_t n_test = static_cast<int32_t>(sel.size());
-    if (n_test_out) *n_test_out = n_test;
-    if (n_test == 0 || p->num_block == 0) return DBSLMM_OK;
-    ARG_CHECK(ctx, diags, "null diags");
-    const int64_t tbps = (tp->n_total + 3) / 4;
-    const int64_t n_rows = (tp->bed_len - 3) / tbps;
-    ARG_CHECK(ctx, tp->bed_len >= 3 + tbps, "test bed image shorter than one SNP row");
-    std::vector<int32_t> tpos(p->n_slots);
-    for (int32_t s = 0; s < p->n_slots; ++s) {
-        const int32_t o = p->h_slot_out[s];
-        int32_t r = -1;
-        if (o >= 0) r = tp->s_pos[o];
-        else if (o != INT32_MIN) r = tp->l_pos[-1 - o];
-        ARG_CHECK(ctx, o == INT32_MIN || (r >= 0 && r < n_rows), "test SNP bed row out of range");
-        tpos[s] = r;
-    }
-    const int64_t nt_pad = round_up(n_test, 64);
-    const int64_t cpitch = nt_pad / 4;          // the compacted rows in the panel image's format
-    const int64_t cbytes = std::max<int64_t>(1, p->n_slots) * cpitch;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    uint8_t *d_tbed = nullptr, *d_cbed = nullptr;
-    int32_t *d_tpos = nullptr, *d_sel = nullptr, *d_cpos = nullptr;
-    double *d_mu = nullptr, *d_rsd = nullptr, *d_Y = nullptr, *d_diags = nullptr;
-    std::vector<int32_t> cpos(p->n_slots);
-    for (int32_t s = 0; s < p->n_slots; ++s) cpos[s] = tpos[s] >= 0 ? s : -1;
-    const size_t ndiag = static_cast<size_t>(n_test) * p->num_block;
-    int rc = DBSLMM_OK;
-    // synchronous allocations and copies: ordered against other host threads' graph captures
-    // (several shards of a multi-device plan on one device)
-    std::lock_guard<std::mutex> lk(g_capture_mu);
-    do {
-        hipError_t e;
-        if ((e = hipMalloc(&d_tbed, tp->bed_len + kBedPad)) != hipSuccess ||
-            (e = hipMemsetAsync(d_tbed, 0, tp->bed_len + kBedPad, st)) != hipSuccess ||
-            (e = upload_staged(d_tbed, tp->bed, tp->bed_len, st)) != hipSuccess ||
-            (e = dev_upload(&d_tpos, tpos, ctx->stream)) != hipSuccess || (e = dev_upload(&d_sel, sel, ctx->stream)) != hipSuccess ||
-            (e = dev_upload(&d_cpos, cpos, ctx->stream)) != hipSuccess ||
-            (e = hipMalloc(&d_cbed, cbytes)) != hipSuccess ||   // (dbslmm_test_compact writes every byte)
-            (e = hipMalloc(&d_mu, std::max<int32_t>(1, p->n_slots) * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_rsd, std::max<int32_t>(1, p->n_slots) * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_Y, std::max<int64_t>(1, p->n_slots) * nt_pad * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_diags, ndiag * sizeof(double))) != hipSuccess ||
-            (e = hipMemsetAsync(d_diags, 0, ndiag * sizeof(double), st)) != hipSuccess) {
-            ctx->err = std::string("variance alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        if (p->n_slots > 0 && p->n_nonempty > 0) {
-            hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cpitch + 255) / 256), p->n_slots),
-                               dim3(256), 0, st, d_tbed, tbps, d_tpos, p->n_slots, d_sel, n_test, cpitch, d_cbed);
-            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
-                               st, d_cbed, n_test, cpitch, d_cpos, p->n_slots, d_mu, d_rsd);
-            hipLaunchKernelGGL(dbslmm_variance, dim3(static_cast<unsigned>(nt_pad / 64), p->n_nonempty),
-                               dim3(256), 0, st, p->d_M + p->var_copy * p->M_elems, p->d_row0, p->d_m,
-                               p->d_ms, p->d_ld, p->d_matoff, p->d_blk_id, p->d_status + p->var_copy * p->nbk,
-                               d_cbed, cpitch, d_mu, d_rsd, n_test,
-                               p->sigma_run, static_cast<double>(p->n_obs), d_Y, nt_pad, d_diags);
-        }
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess ||
-            (e = hipMemcpy(diags, d_diags, ndiag * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) {
-            ctx->err = std::string("variance run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-        }
-    } while (0);
-    void* bufs[] = {d_tbed, d_cbed, d_tpos, d_sel, d_cpos, d_mu, d_rsd, d_Y, d_diags};
-    for (void* q : bufs)
-        if (q) (void)hipFree(q);
-    return rc;
-}
-
-// Polygenic scores of the test panel for every copy of the latest run (score.hip).  Two feeders of
-// one kernel: all individuals selected -> the test .bed as a panel image (repitch + row table; the
-// per-slot statistics gathered from the table, rows gathered by the slots' test rows); a subset ->
-// the variance path's compaction + statistics, rows in slot order.
-int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_score_args* args,
-                      int32_t n_copies, double* scores, int32_t* dropped, int32_t* n_test_out,
-                      double* gpu_ms) {
-    if (!p) return DBSLMM_E_ARG;
-    dbslmm_ctx* ctx = p->ctx;
-    if (!p->ran) { ctx->err = "plan_score before plan_run"; return DBSLMM_E_STATE; }
-    if (p->stopped) { ctx->err = "plan_score after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
-    ARG_CHECK(ctx, tp && tp->bed && tp->n_total > 0, "bad test panel");
-    const int32_t mode = args ? args->mode : DBSLMM_SCORE_COUNTS;
-    ARG_CHECK(ctx, mode == DBSLMM_SCORE_COUNTS || mode == DBSLMM_SCORE_STD, "score mode");
-    ARG_CHECK(ctx, !args || args->chunk_slots >= 0, "chunk_slots must be >= 0");
-    ARG_CHECK(ctx, n_copies == p->score_copies, "n_copies must equal the copies of the latest run");
-    ARG_CHECK(ctx, p->n_s == 0 || tp->s_pos, "test panel s_pos missing");
-    ARG_CHECK(ctx, p->n_l == 0 || tp->l_pos, "test panel l_pos missing");
-    if (p->mp) return mp_score(p, tp, args, n_copies, scores, dropped, n_test_out, gpu_ms);
-    if (p->score_stale) {
-        ctx->err = "plan_score after plan_variance re-solved the latest sigma (the device results of copy 0 are "
-                   "overwritten): score before the variance, or run again";
-        return DBSLMM_E_STATE;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (const int rc = pcg_finish(p)) return rc;       // a run still pending
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (const int rc = check_trsv(p)) return rc;
-    std::vector<int32_t> sel;
-    bool all = true;
-    if (tp->indicator) {
-        for (int32_t i = 0; i < tp->n_total; ++i) {
-            if (tp->indicator[i] != 0) sel.push_back(i);
-            else all = false;
-        }
-    }
-    const int32_t n_test = all ? tp->n_total : static_cast<int32_t>(sel.size());
-    if (n_test_out) *n_test_out = n_test;
-    if (gpu_ms) *gpu_ms = 0.0;
-    const int64_t tbps = (tp->n_total + 3) / 4;
-    ARG_CHECK(ctx, tp->bed_len >= 3 + tbps, "test bed image shorter than one SNP row");
-    const int64_t n_rows = (tp->bed_len - 3) / tbps;
-    ARG_CHECK(ctx, n_rows < INT32_MAX, "test bed image has too many rows");
-    std::vector<int32_t> tpos(p->n_slots);
-    for (int32_t s = 0; s < p->n_slots; ++s) {
-        const int32_t o = p->h_slot_out[s];
-        int32_t r = -1;
-        if (o >= 0) r = tp->s_pos[o];
-        else if (o != INT32_MIN) r = tp->l_pos[-1 - o];
-        ARG_CHECK(ctx, o == INT32_MIN || (r >= 0 && r < n_rows), "test SNP bed row out of range");
-        tpos[s] = r;
-    }
-    if (n_test == 0) {
-        if (dropped) std::fill(dropped, dropped + n_copies, 0);
-        return DBSLMM_OK;
-    }
-    ARG_CHECK(ctx, scores, "null scores");
-    const size_t n_out = static_cast<size_t>(n_copies) * n_test;
-    if (p->n_slots == 0 || p->n_nonempty == 0) {       // no SNP: every score is the empty sum
-        std::fill(scores, scores + n_out, 0.0);
-        if (dropped) std::fill(dropped, dropped + n_copies, 0);
-        return DBSLMM_OK;
-    }
-    // (a multiple of the kernel's prefetch depth: a chunk_slots between two multiples acts as the next one)
-    const int32_t chunk_slots = static_cast<int32_t>(std::min<int64_t>(
-        round_up(args && args->chunk_slots > 0 ? args->chunk_slots : score::kChunkSlots, score::kDepth), 1 << 30));
-    const int32_t n_chunks = (p->n_slots + chunk_slots - 1) / chunk_slots;
-    const int64_t stride64 = static_cast<int64_t>(n_chunks) * chunk_slots;   // slots incl. the last chunk's tail
-    ARG_CHECK(ctx, stride64 + score::kDepth < INT32_MAX, "chunk_slots too large");
-    const int32_t stride = static_cast<int32_t>(stride64);
-    const int32_t n_words = (n_test + 15) / 16;
-    const int64_t n_pad = 16 * static_cast<int64_t>(n_words);
-    ARG_CHECK(ctx, n_chunks <= 65535, "chunk_slots too small for this plan (more than 65535 chunks)");
-    const int64_t cpitch = round_up(n_test, 256) / 4;   // the compacted rows in the panel image's format
-    std::vector<int32_t> cpos(p->n_slots);
-    for (int32_t s = 0; s < p->n_slots; ++s) cpos[s] = tpos[s] >= 0 ? s : -1;
-    // the row the product kernel loads for every slot it may touch (a chunk's tail and the
-    // prefetch past it included): a padding slot and the tail read a valid row with a = 0 --
-    // image feeder: the image's zero-dosage row; compaction feeder: the slot's own row (all 11), row 0
-    std::vector<int32_t> srow(static_cast<size_t>(stride) + score::kDepth);
-    for (size_t s = 0; s < srow.size(); ++s) {
-        const bool real = s < static_cast<size_t>(p->n_slots);
-        if (all) srow[s] = real && tpos[s] >= 0 ? tpos[s] : static_cast<int32_t>(n_rows);
-        else srow[s] = real ? static_cast<int32_t>(s) : 0;
-    }
-    std::vector<double> hw_s, hw_l;
-    std::vector<uint8_t> hf_s, hf_l;
-    if (args && args->w_s) hw_s.assign(args->w_s, args->w_s + p->n_s);
-    if (args && args->w_l) hw_l.assign(args->w_l, args->w_l + p->n_l);
-    if (args && args->flip_s) hf_s.assign(args->flip_s, args->flip_s + p->n_s);
-    if (args && args->flip_l) hf_l.assign(args->flip_l, args->flip_l + p->n_l);
-    hipStream_t st = ctx->stream;
-    uint8_t *d_tbed = nullptr, *d_cbed = nullptr, *d_fs = nullptr, *d_fl = nullptr;
-    int32_t *d_tpos = nullptr, *d_sel = nullptr, *d_cpos = nullptr, *d_drop = nullptr, *d_srow = nullptr;
-    double *d_mu = nullptr, *d_rsd = nullptr, *d_ws = nullptr, *d_wl = nullptr, *d_coef = nullptr, *d_kc = nullptr,
-           *d_part = nullptr, *d_scores = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    PanelImage im;
-    const size_t nsl = static_cast<size_t>(p->n_slots);
-    const size_t ncoef = static_cast<size_t>(n_copies) * stride;
-    const int pass_max = std::min<int>(score::kMaxPass, n_copies);
-    int rc = DBSLMM_OK;
-    // synchronous allocations: ordered against other host threads' graph captures
-    std::lock_guard<std::mutex> lk(g_capture_mu);
-    do {
-        hipError_t e;
-        if ((e = hipMalloc(&d_tbed, tp->bed_len + kBedPad)) != hipSuccess ||
-            (e = hipMemsetAsync(d_tbed, 0, tp->bed_len + kBedPad, st)) != hipSuccess ||
-            (e = upload_staged(d_tbed, tp->bed, tp->bed_len, st)) != hipSuccess ||
-            (e = dev_upload(&d_tpos, tpos, st)) != hipSuccess || (e = dev_upload(&d_srow, srow, st)) != hipSuccess ||
-            (e = hipMalloc(&d_mu, nsl * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_rsd, nsl * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_coef, 3 * ncoef * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_kc, static_cast<size_t>(n_copies) * (1 + n_chunks) * sizeof(double))) != hipSuccess ||   // K_c | per chunk
-            (e = hipMalloc(&d_drop, n_copies * sizeof(int32_t))) != hipSuccess ||
-            (e = hipMemsetAsync(d_drop, 0, n_copies * sizeof(int32_t), st)) != hipSuccess ||
-            (e = hipMalloc(&d_part, static_cast<size_t>(n_chunks) * pass_max * n_pad * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_scores, n_out * sizeof(double))) != hipSuccess ||
-            (!hw_s.empty() && (e = dev_upload(&d_ws, hw_s, st)) != hipSuccess) ||
-            (!hw_l.empty() && (e = dev_upload(&d_wl, hw_l, st)) != hipSuccess) ||
-            (!hf_s.empty() && (e = dev_upload(&d_fs, hf_s, st)) != hipSuccess) ||
-            (!hf_l.empty() && (e = dev_upload(&d_fl, hf_l, st)) != hipSuccess) ||
-            (e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) {
-            ctx->err = std::string("score alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        const uint8_t* rows = nullptr;    // the 2-bit rows the product reads and their pitch
-        int64_t pitch = 0;
-        if (all) {
-            if ((e = image_from_verbatim(ctx, d_tbed, tp->bed_len, tp->n_total, &im)) != hipSuccess) {
-                ctx->err = std::string("score panel image: ") + hipGetErrorString(e);
-                rc = DBSLMM_E_HIP;
-                break;
-            }
-            hipLaunchKernelGGL(dbslmm_slot_stats, dim3((p->n_slots + 255) / 256), dim3(256), 0, st, im.rows(),
-                               tp->n_total, d_tpos, nullptr, p->n_slots, nullptr, d_mu, d_rsd, nullptr);
-            rows = im.mem.get();
-            pitch = im.pitch;
-        } else {
-            if ((e = dev_upload(&d_sel, sel, st)) != hipSuccess || (e = dev_upload(&d_cpos, cpos, st)) != hipSuccess ||
-                (e = hipMalloc(&d_cbed, nsl * cpitch)) != hipSuccess) {   // (dbslmm_test_compact writes every byte)
-                ctx->err = std::string("score alloc/upload: ") + hipGetErrorString(e);
-                rc = DBSLMM_E_HIP;
-                break;
-            }
-            for (int32_t q0 = 0; q0 < p->n_slots; q0 += 32768) {   // (one grid row per slot)
-                const int32_t nq = std::min<int32_t>(32768, p->n_slots - q0);
-                hipLaunchKernelGGL(dbslmm_test_compact, dim3(static_cast<unsigned>((cpitch + 255) / 256), nq),
-                                   dim3(256), 0, st, d_tbed, tbps, d_tpos + q0, nq, d_sel, n_test, cpitch,
-                                   d_cbed + static_cast<int64_t>(q0) * cpitch);
-            }
-            hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
-                               st, d_cbed, n_test, cpitch, d_cpos, p->n_slots, d_mu, d_rsd);
-            rows = d_cbed;
-            pitch = cpitch;
-        }
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev0, st)) != hipSuccess) {
-            ctx->err = std::string("score statistics: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        double *d_a = d_coef, *d_am = d_coef + ncoef, *d_k = d_coef + 2 * ncoef;
-        hipLaunchKernelGGL(dbslmm_score_coef, dim3((stride + 255) / 256, n_copies), dim3(256), 0, st,
-                           p->d_slot_out, p->d_slot_block, p->d_blk_id, p->d_status, p->nbk, p->d_beta_s,
-                           p->d_beta_l, p->n_s, p->n_l, d_ws, d_wl, d_fs, d_fl, d_mu, d_rsd, p->n_slots, stride,
-                           n_copies, mode, n_test, d_a, d_am, d_k, d_drop);
-        hipLaunchKernelGGL(dbslmm_score_const, dim3(n_chunks, n_copies), dim3(256), 0, st, d_k, stride, chunk_slots,
-                           static_cast<int64_t>(stride), d_kc + n_copies);
-        hipLaunchKernelGGL(dbslmm_score_const, dim3(1, n_copies), dim3(256), 0, st, d_kc + n_copies, n_chunks, n_chunks,
-                           static_cast<int64_t>(n_chunks), d_kc);
-        const dim3 pgrid((n_words + 255) / 256, n_chunks);
-        for (int c0 = 0; c0 < n_copies; c0 += score::kMaxPass) {   // at most kMaxPass copies per pass
-            const int nc = std::min<int>(score::kMaxPass, n_copies - c0);
-            const double* pa = d_a + static_cast<size_t>(c0) * stride;
-            const double* pam = d_am + static_cast<size_t>(c0) * stride;
-#define DBSLMM_SCORE_PASS(NC)                                                                                   \
-    hipLaunchKernelGGL(dbslmm_score_partial<NC>, pgrid, dim3(256), 0, st, rows, pitch, d_srow, pa, pam, stride, \
-                       chunk_slots, n_words, d_part)
-            if (nc == 1) DBSLMM_SCORE_PASS(1);
-            else if (nc == 2) DBSLMM_SCORE_PASS(2);
-            else if (nc == 3) DBSLMM_SCORE_PASS(3);
-            else DBSLMM_SCORE_PASS(4);
-#undef DBSLMM_SCORE_PASS
-            hipLaunchKernelGGL(dbslmm_score_reduce, dim3((n_test + 255) / 256, nc), dim3(256), 0, st, d_part, n_chunks,
-                               nc, n_pad, d_kc + c0, n_test, d_scores + static_cast<size_t>(c0) * n_test);
-        }
-        float ms = 0.0f;
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev1, st)) != hipSuccess ||
-            (e = hipMemcpyAsync(scores, d_scores, n_out * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-            (dropped && (e = hipMemcpyAsync(dropped, d_drop, n_copies * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) ||
-            (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) {
-            ctx->err = std::string("score run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        if (gpu_ms) *gpu_ms = ms;
-    } while (0);
-    void* bufs[] = {d_tbed, d_cbed, d_fs, d_fl, d_tpos, d_sel, d_cpos, d_drop, d_srow, d_mu, d_rsd, d_ws, d_wl, d_coef, d_kc, d_part, d_scores};
-    for (void* q : bufs)
-        if (q) (void)hipFree(q);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
-}
-
-// MAF pass over the first n_snp rows (IO::readBim, dtpr.cpp:93-102).
-int dbslmm_bed_maf(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
-                   int64_t n_snp, double* maf) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ARG_CHECK(ctx, bed && maf && n_ref > 1 && n_snp >= 0 && n_snp < INT32_MAX, "bad arguments");
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
-    ARG_CHECK(ctx, bed_len >= 3 + n_snp * bps, "bed image shorter than n_snp rows");
-    if (n_snp == 0) return DBSLMM_OK;
-    if (!ctx->subs.empty()) return mp_bed_maf(ctx, bed, n_ref, n_snp, maf);
-    KEY_CHECK(ctx, bed, bed_len, n_ref);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PanelImage im;            // the context's cached image of this host range, or an upload of our own
-    char* d_work = nullptr;   // one allocation: mu | S | maf (doubles), then the per-row missing flags
-    int rc = DBSLMM_OK;
-    do {
-        hipError_t e;
-        const size_t nd = static_cast<size_t>(n_snp) * sizeof(double);
-        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
-            (e = hipMalloc(&d_work, 3 * nd + n_snp * sizeof(int32_t))) != hipSuccess ||
-            (e = hipMemsetAsync(d_work + 3 * nd, 0, n_snp * sizeof(int32_t), ctx->stream)) != hipSuccess) {
-            ctx->err = std::string("bed_maf alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        double* d_mu = reinterpret_cast<double*>(d_work);
-        double* d_S = d_mu + n_snp;
-        double* d_maf = d_S + n_snp;
-        int32_t* d_miss = reinterpret_cast<int32_t*>(d_maf + n_snp);
-        const uint8_t* db = im.mem.get();
-        // from the image's row table: row k = image row k (null row lists); per-row missing-call
-        // flags (row k's "block" is k)
-        hipLaunchKernelGGL(dbslmm_slot_stats, dim3(static_cast<unsigned>((n_snp + 255) / 256)), dim3(256), 0,
-                           ctx->stream, im.rows(), n_ref, nullptr, nullptr, static_cast<int32_t>(n_snp),
-                           d_S, d_mu, nullptr, d_miss);
-        hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_snp + 255) / 256)), dim3(256), 0,
-                           ctx->stream, db, n_ref, im.pitch, nullptr, static_cast<int32_t>(n_snp), d_mu, d_maf,
-                           d_S, d_miss);
-        if ((e = hipGetLastError()) != hipSuccess ||
-            (e = hipMemcpyAsync(maf, d_maf, nd, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-            ctx->err = std::string("bed_maf run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-        }
-    } while (0);
-    (void)hipFree(d_work);
-    return rc;
-}
-
-// The row table of the panel's image, rows [0, n_rows): the exact integers {sum, sumsq, nmiss}.
-int dbslmm_bed_row_stats(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
-                         int64_t n_rows, int32_t* out) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ON_FIRST_DEVICE(ctx, dbslmm_bed_row_stats(ctx0_, bed, bed_len, n_ref, n_rows, out));
-    ARG_CHECK(ctx, bed && out && n_ref > 1 && n_rows >= 0 && n_rows < INT32_MAX, "bad arguments");
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
-    ARG_CHECK(ctx, bed_len >= 3 + n_rows * bps, "bed image shorter than n_rows rows");
-    if (n_rows == 0) return DBSLMM_OK;
-    KEY_CHECK(ctx, bed, bed_len, n_ref);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PanelImage im;
-    hipError_t e = panel_image(ctx, bed, bed_len, n_ref, &im);
-    std::vector<int32_t> h(static_cast<size_t>(n_rows) * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), im.rows(), h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        ctx->err = std::string("bed_row_stats: ") + hipGetErrorString(e);
-        return DBSLMM_E_HIP;
-    }
-    for (int64_t r = 0; r < n_rows; ++r)
-        for (int k = 0; k < 3; ++k) out[3 * r + k] = h[4 * r + k];
-    return DBSLMM_OK;
-}
-
-int dbslmm_read_snp_std(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
-                        const int32_t* pos, int32_t n_rows, double* out, double* maf) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ON_FIRST_DEVICE(ctx, dbslmm_read_snp_std(ctx0_, bed, bed_len, n_ref, pos, n_rows, out, maf));
-    if (const int rc = ctx_ready(ctx)) return rc;
-    ARG_CHECK(ctx, bed && pos && out && n_ref > 1 && n_rows >= 0, "bad arguments");
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
-    for (int32_t j = 0; j < n_rows; ++j)
-        ARG_CHECK(ctx, pos[j] >= 0 && 3 + (pos[j] + 1) * bps <= bed_len, "row out of range");
-    if (n_rows == 0) return DBSLMM_OK;
-    KEY_CHECK(ctx, bed, bed_len, n_ref);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PanelImage im;
-    int32_t* d_pos = nullptr;
-    double *d_mu = nullptr, *d_rsd = nullptr, *d_maf = nullptr, *d_out = nullptr;
-    std::vector<int32_t> hp(pos, pos + n_rows);
-    const int64_t n_out = static_cast<int64_t>(n_rows) * n_ref;
-    int rc = DBSLMM_OK;
-    do {
-        hipError_t e;
-        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
-            (e = dev_upload(&d_pos, hp, ctx->stream)) != hipSuccess ||
-            (e = hipMalloc(&d_mu, n_rows * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_rsd, n_rows * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_maf, n_rows * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_out, n_out * sizeof(double))) != hipSuccess) {
-            ctx->err = std::string("read_snp_std alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        const uint8_t* db = im.mem.get();
-        hipLaunchKernelGGL(dbslmm_slot_stats, dim3((n_rows + 255) / 256), dim3(256), 0, ctx->stream,
-                           im.rows(), n_ref, d_pos, nullptr, n_rows, nullptr, d_mu, d_rsd, nullptr);
-        hipLaunchKernelGGL(dbslmm_maf_arma, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
-                           ctx->stream, db, n_ref, im.pitch, d_pos, n_rows, d_mu, d_maf, nullptr, nullptr);
-        hipLaunchKernelGGL(dbslmm_std_columns, dim3(static_cast<unsigned>((n_out + 255) / 256)),
-                           dim3(256), 0, ctx->stream, db, n_ref, im.pitch, d_pos, n_rows, d_mu, d_rsd,
-                           d_out);
-        if ((e = hipGetLastError()) != hipSuccess ||
-            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess ||
-            (e = hipMemcpy(out, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess ||
-            (maf && (e = hipMemcpy(maf, d_maf, n_rows * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)) {
-            ctx->err = std::string("read_snp_std run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-        }
-    } while (0);
-    (void)hipFree(d_pos);
-    (void)hipFree(d_mu);
-    (void)hipFree(d_rsd);
-    (void)hipFree(d_maf);
-    (void)hipFree(d_out);
-    return rc;
-}
-
-// External-validation terms of the `valid` tool (scr/validate.cpp:221-257).
-int dbslmm_valid_blocks(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref,
-                        int32_t num_block, const int64_t* ptr, const int32_t* pos,
-                        const double* z1, const double* z2, double* nume, double* deno) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ON_FIRST_DEVICE(ctx, dbslmm_valid_blocks(ctx0_, bed, bed_len, n_ref, num_block, ptr, pos, z1, z2, nume, deno));
-    if (const int rc = ctx_ready(ctx)) return rc;
-    ARG_CHECK(ctx, bed && ptr && nume && deno && n_ref > 1 && num_block >= 0, "bad arguments");
-    const int64_t bps = n_ref / 4 + (n_ref % 4 ? 1 : 0);
-    const int64_t n_rows = ptr[num_block];
-    ARG_CHECK(ctx, n_rows >= 0 && n_rows < INT32_MAX && (n_rows == 0 || (pos && z1 && z2)), "bad CSR");
-    for (int b = 0; b < num_block; ++b) ARG_CHECK(ctx, ptr[b + 1] >= ptr[b], "CSR offsets not monotone");
-    for (int64_t j = 0; j < n_rows; ++j)
-        ARG_CHECK(ctx, pos[j] >= 0 && 3 + (pos[j] + 1) * bps <= bed_len, "row out of range");
-    // nume = z1 . z2 per block (host: O(m), in the reference's accumulation order)
-    for (int b = 0; b < num_block; ++b) {
-        double t = 0.0;
-        for (int64_t j = ptr[b]; j < ptr[b + 1]; ++j) t += z1[j] * z2[j];
-        nume[b] = t;
-    }
-    if (num_block == 0) return DBSLMM_OK;
-    KEY_CHECK(ctx, bed, bed_len, n_ref);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int64_t n_words = (n_ref + 15) / 16;
-    const int32_t n_chunks = static_cast<int32_t>((n_words + 255) / 256);
-    PanelImage im;
-    int32_t* d_pos = nullptr;
-    int64_t* d_ptr = nullptr;
-    double *d_z1 = nullptr, *d_mu = nullptr, *d_rsd = nullptr, *d_part = nullptr, *d_deno = nullptr;
-    std::vector<int32_t> hp(pos, pos + n_rows);
-    std::vector<int64_t> hptr(ptr, ptr + num_block + 1);
-    std::vector<double> hz(z1, z1 + n_rows);
-    const size_t nr = std::max<int64_t>(1, n_rows);
-    int rc = DBSLMM_OK;
-    do {
-        hipError_t e;
-        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
-            (e = dev_upload(&d_pos, hp, ctx->stream)) != hipSuccess || (e = dev_upload(&d_ptr, hptr, ctx->stream)) != hipSuccess ||
-            (e = dev_upload(&d_z1, hz, ctx->stream)) != hipSuccess ||
-            (e = hipMalloc(&d_mu, nr * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_rsd, nr * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_part, static_cast<size_t>(num_block) * n_chunks * sizeof(double))) != hipSuccess ||
-            (e = hipMalloc(&d_deno, num_block * sizeof(double))) != hipSuccess) {
-            ctx->err = std::string("valid alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        const uint8_t* db = im.mem.get();
-        if (n_rows > 0)
-            hipLaunchKernelGGL(dbslmm_slot_stats, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
-                               ctx->stream, im.rows(), n_ref, d_pos, nullptr, static_cast<int32_t>(n_rows),
-                               nullptr, d_mu, d_rsd, nullptr);
-        // grid rows stride over the blocks, so num_block is not bound by the grid-row limit
-        constexpr int32_t kValidGridY = 65535;
-        hipLaunchKernelGGL(dbslmm_valid_partial, dim3(n_chunks, std::min(num_block, kValidGridY)), dim3(256), 0,
-                           ctx->stream, db, n_ref, im.pitch, d_ptr, d_pos, d_z1, d_mu, d_rsd, d_part, n_chunks,
-                           num_block);
-        hipLaunchKernelGGL(dbslmm_valid_reduce, dim3((num_block + 255) / 256), dim3(256), 0, ctx->stream,
-                           d_part, n_chunks, num_block, static_cast<double>(n_ref), d_deno);
-        if ((e = hipGetLastError()) != hipSuccess ||
-            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess ||
-            (e = hipMemcpy(deno, d_deno, num_block * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) {
-            ctx->err = std::string("valid run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-        }
-    } while (0);
-    void* bufs[] = {d_pos, d_ptr, d_z1, d_mu, d_rsd, d_part, d_deno};
-    for (void* q : bufs)
-        if (q) (void)hipFree(q);
-    return rc;
-}
-
-// dbslmm_r2_tiles over the tiles of L on the panel's image: mask mode (h_masks: kClumpMaskWords words
-// per tile; chr / bp in position order) or value mode (h_r2: n x n doubles).  pos = the bed rows in
-// position order.  Every transfer on the context's stream; complete on return.
-static int r2_tiles_run(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, const ClumpLayout& L,
-                        const std::vector<int32_t>& pos, const std::vector<int32_t>* chr,
-                        const std::vector<int64_t>* bp, double thr, int64_t window, uint32_t* h_masks,
-                        double* h_r2, double* gpu_ms) {
-    PanelImage im;
-    int32_t *d_pos = nullptr, *d_chr = nullptr;
-    int64_t* d_bp = nullptr;
-    ClumpTile* d_tiles = nullptr;
-    uint32_t* d_masks = nullptr;
-    double* d_r2 = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const int32_t n_tiles = static_cast<int32_t>(L.tiles.size());
-    const size_t mask_bytes = static_cast<size_t>(n_tiles) * kClumpMaskWords * sizeof(uint32_t);
-    const size_t r2_bytes = static_cast<size_t>(L.n) * L.n * sizeof(double);
-    int rc = DBSLMM_OK;
-    do {
-        hipError_t e;
-        if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess ||
-            (e = dev_upload(&d_pos, pos, ctx->stream)) != hipSuccess ||
-            (e = dev_upload(&d_tiles, L.tiles, ctx->stream)) != hipSuccess ||
-            (chr && (e = dev_upload(&d_chr, *chr, ctx->stream)) != hipSuccess) ||
-            (bp && (e = dev_upload(&d_bp, *bp, ctx->stream)) != hipSuccess) ||
-            (h_masks && (e = hipMalloc(&d_masks, mask_bytes)) != hipSuccess) ||
-            (h_r2 && (e = hipMalloc(&d_r2, r2_bytes)) != hipSuccess) ||
-            (e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess ||
-            (e = hipEventRecord(ev0, ctx->stream)) != hipSuccess) {
-            ctx->err = std::string("r2 tiles alloc/upload: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        const int64_t kpad = im.pitch * 4;
-        const dim3 grid(static_cast<unsigned>((n_tiles + 3) / 4));
-        if (h_masks)
-            hipLaunchKernelGGL(dbslmm_r2_tiles<true>, grid, dim3(256), 0, ctx->stream, im.mem.get(), kpad, im.rows(),
-                               im.n_rows, n_ref, d_pos, L.n, d_tiles, n_tiles, d_chr, d_bp, thr, window, d_masks,
-                               static_cast<double*>(nullptr));
-        else
-            hipLaunchKernelGGL(dbslmm_r2_tiles<false>, grid, dim3(256), 0, ctx->stream, im.mem.get(), kpad, im.rows(),
-                               im.n_rows, n_ref, d_pos, L.n, d_tiles, n_tiles, static_cast<const int32_t*>(nullptr),
-                               static_cast<const int64_t*>(nullptr), 0.0, int64_t(0), static_cast<uint32_t*>(nullptr),
-                               d_r2);
-        float ms = 0.0f;
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev1, ctx->stream)) != hipSuccess ||
-            (h_masks && (e = hipMemcpyAsync(h_masks, d_masks, mask_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
-            (h_r2 && (e = hipMemcpyAsync(h_r2, d_r2, r2_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
-            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) {
-            ctx->err = std::string("r2 tiles run: ") + hipGetErrorString(e);
-            rc = DBSLMM_E_HIP;
-            break;
-        }
-        if (gpu_ms) *gpu_ms = ms;
-    } while (0);
-    void* bufs[] = {d_pos, d_chr, d_bp, d_tiles, d_masks, d_r2};
-    for (void* q : bufs)
-        if (q) (void)hipFree(q);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    return rc;
-}
-
-// the row-list checks shared by dbslmm_ld_r2 and dbslmm_clump
-static int r2_rows_check(dbslmm_ctx* ctx, int64_t bed_len, int32_t n_ref, const int32_t* pos, int32_t n_rows) {
-    ARG_CHECK(ctx, 9 * round_up(n_ref, gram::kKpadAlign) < (int64_t(1) << 24),
-              "n_ref past the FP4 Gram's exact range (9 * roundup(n_ref, 256) < 2^24)");
-    const int64_t bps = bed_row_bytes(n_ref);
-    for (int32_t j = 0; j < n_rows; ++j)
-        ARG_CHECK(ctx, pos[j] >= 0 && 3 + (static_cast<int64_t>(pos[j]) + 1) * bps <= bed_len, "row out of range");
-    return DBSLMM_OK;
-}
-
-// LD r2 of every pair of the listed rows (clump.hip, value mode).
-int dbslmm_ld_r2(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, const int32_t* pos,
-                 int32_t n_rows, double* r2) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ON_FIRST_DEVICE(ctx, dbslmm_ld_r2(ctx0_, bed, bed_len, n_ref, pos, n_rows, r2));
-    ARG_CHECK(ctx, bed && n_ref > 1 && n_rows >= 0 && n_rows <= 8192 && (n_rows == 0 || (pos && r2)), "bad arguments");
-    if (const int rc = r2_rows_check(ctx, bed_len, n_ref, pos, n_rows)) return rc;
-    if (n_rows == 0) return DBSLMM_OK;
-    KEY_CHECK(ctx, bed, bed_len, n_ref);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const ClumpLayout L = build_dense_layout(n_rows);
-    return r2_tiles_run(ctx, bed, bed_len, n_ref, L, std::vector<int32_t>(pos, pos + n_rows), nullptr, nullptr, 0.0, 0,
-                        nullptr, r2, nullptr);
-}
-
-// Clumping (software/DBSLMM.R:139-145, `plink --clump`): the index SNPs of the candidates.
-int dbslmm_clump(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_cand,
-                 const int32_t* pos, const int32_t* chr, const int64_t* bp, const dbslmm_clump_args* args,
-                 int32_t* index_of, int32_t* n_index, double* gpu_ms) {
-    if (!ctx) return DBSLMM_E_ARG;
-    ON_FIRST_DEVICE(ctx, dbslmm_clump(ctx0_, bed, bed_len, n_ref, n_cand, pos, chr, bp, args, index_of, n_index, gpu_ms));
-    ARG_CHECK(ctx, bed && args && n_ref > 1 && n_cand >= 0 && (n_cand == 0 || (pos && chr && bp && index_of)),
-              "bad arguments");
-    ARG_CHECK(ctx, args->r2 > 0.0 && args->r2 <= 1.0, "clump r2 threshold outside (0, 1]");
-    ARG_CHECK(ctx, args->window_bp >= 0, "clump window below 0");
-    if (const int rc = r2_rows_check(ctx, bed_len, n_ref, pos, n_cand)) return rc;
-    if (n_index) *n_index = 0;
-    if (gpu_ms) *gpu_ms = 0.0;
-    if (n_cand == 0) return DBSLMM_OK;
-    ClumpLayout L = build_clump_layout(n_cand, chr, bp, args->window_bp);
-    clump_index_columns(L);
-    std::vector<uint32_t> masks(L.tiles.size() * kClumpMaskWords);
-    if (!L.tiles.empty()) {
-        KEY_CHECK(ctx, bed, bed_len, n_ref);
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        std::vector<int32_t> spos(static_cast<size_t>(n_cand)), schr(static_cast<size_t>(n_cand));
-        std::vector<int64_t> sbp(static_cast<size_t>(n_cand));
-        for (int32_t p = 0; p < n_cand; ++p) {
-            const int32_t k = L.order[static_cast<size_t>(p)];
-            spos[static_cast<size_t>(p)] = pos[k];
-            schr[static_cast<size_t>(p)] = chr[k];
-            sbp[static_cast<size_t>(p)] = bp[k];
-        }
-        if (const int rc = r2_tiles_run(ctx, bed, bed_len, n_ref, L, spos, &schr, &sbp, args->r2, args->window_bp,
-                                        masks.data(), nullptr, gpu_ms))
-            return rc;
-    }
-    const int32_t ni = clump_greedy(L, masks.data(), index_of);
-    if (n_index) *n_index = ni;
-    return DBSLMM_OK;
-}
+#include "panel_api.hip"   // the test-panel and .bed entry points (variance, score, MAF, row lists, clumping)
 
 #ifdef DBSLMM_STAMPS
 // diagnostic build only (libdbslmm_hip_stamps.so): read + clear the per-phase tick counters

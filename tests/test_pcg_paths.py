@@ -492,6 +492,42 @@ def test_route_sequence_with_variance_and_copy_counts():
 
 
 @pytest.mark.gpu
+def test_one_plan_takes_every_reallocation_path():
+    """One plan's life through every place that frees and re-allocates its device buffers: PCG
+    run_multi(3) (pcg_layout), PCG run_multi(2) (pcg_layout rebuilt for another copy count),
+    run_multi of 5 copies (the factorisation: ensure_copies grows the per-copy buffers and the block
+    matrices, the first merged work list and Chebyshev coefficients), run_multi of 6 copies (the
+    merged work list replaced, a longer coefficient vector: one more copy group), variance(),
+    close() -- each call the bits of the same call on a fresh plan."""
+    from dbslmm_amd import Context, Plan
+    c = pcg_case()
+    prob = c.prob
+    s3, s2 = _sig(prob), _sig(prob, (0.9, 1.1))
+    s5, s6 = _sig(prob, FIVE), _sig(prob, FIVE + (1.6,))
+    cheb = {}
+
+    def multi(sig):
+        def call(p):
+            out = p.run_multi(sig)
+            cheb[len(sig)] = p.workload()
+            return out
+        return call
+    refs = [_fresh(prob, multi(s)) for s in (s3, s2, s5, s6)]
+    refv = _fresh(prob, lambda p: (p.run_multi(s6), _variance(p, c))[1])
+    # the fresh runs took the paths this test is about: both many-copy runs iterate their other
+    # copies on the base copy's factor, the second with more copy groups (a longer coefficient vector)
+    assert cheb[5]["cheb_base"] >= 0 and cheb[6]["cheb_base"] >= 0
+    assert 0 < cheb[5]["cheb_iters"] < cheb[6]["cheb_iters"], (cheb[5]["cheb_iters"], cheb[6]["cheb_iters"])
+    plan = Plan(Context(0), prob)
+    for sig, ref, route in zip((s3, s2, s5, s6), refs, (1, 1, 0, 0)):
+        _same(plan.run_multi(sig), ref)
+        _route(plan, route)
+        assert plan.workload()["cheb_iters"] == cheb[len(sig)]["cheb_iters"]
+    np.testing.assert_array_equal(_variance(plan, c), refv)
+    plan.close()
+
+
+@pytest.mark.gpu
 def test_runs_without_sync_and_queries_on_a_pending_run():
     """A PCG run stays pending until something waits for it: run() twice without sync() and then
     download(); run() then variance(); run() then block_iters() -- each the result of the
