@@ -10,6 +10,8 @@ entry points mirror the reference operator interface (fboehm/DBSLMM, scr/dbslmmf
 * ``read_snp_std``        -- IO::readSNPIm + SNPPROC::nomalizeVec for a list of rows.
 * ``clump``               -- the index SNPs of a candidate list by PLINK's greedy clumping rule on the
   reference panel (software/DBSLMM.R:139-145), ``ld_r2`` the dense r2 matrix of a list of rows.
+* ``ld_scores``           -- the LD scores of listed panel rows, ``ldsc_h2`` the LD score regression on
+  them: the heritability the reference takes from an LDSC run (Rmd/Manual.Rmd:170).
 * ``Plan.score``          -- the polygenic scores of a target panel for every h2f copy of the latest
   run (what the reference leaves to ``plink --score``), ``tune_r2`` the R2 index of TUNE.R on them.
 * ``Context.row_stats``   -- the exact per-row integers (sum, sum of squares, missing calls) the
@@ -28,7 +30,7 @@ from . import _lib
 from ._lib import (WORKLOAD_LEN, BLOCK_EMPTY, BLOCK_MONOMORPHIC, BLOCK_NOT_CONVERGED, BLOCK_NOT_PD,
                    BLOCK_OK, KERNEL_NAMES, SOLVER_AUTO, SOLVER_FACTOR, SOLVER_PCG, DbslmmError)
 
-__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2", "ld_r2", "clump",
+__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2", "ld_r2", "clump", "ld_scores", "ldsc_h2",
            "DbslmmError", "BLOCK_OK", "BLOCK_EMPTY", "BLOCK_NOT_PD", "BLOCK_MONOMORPHIC",
            "BLOCK_NOT_CONVERGED", "KERNEL_NAMES", "SOLVER_AUTO", "SOLVER_FACTOR", "SOLVER_PCG"]
 
@@ -447,6 +449,50 @@ def clump(ctx: Context, bed: np.ndarray, n_ref: int, rows, chrom, bp, r2: float 
                                    C.byref(args), _ptr(out), None, _ptr(ms)), "clump")
     ctx.clump_gpu_ms = float(ms[0])
     return out[:len(rows)]
+
+
+def ld_scores(ctx: Context, bed: np.ndarray, n_ref: int, rows, chrom, bp, kb: float = 1000, unbiased: bool = True,
+              max_tiles: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """LD scores (dbslmm_ld_scores) of the bed rows `rows` with chromosome codes `chrom` and base pairs
+    `bp`, in any order: (l2, n_window).  l2[k] = the sum over the listed rows within `kb` of row k on
+    its chromosome (k included) of r2, with ldsc's adjustment r2 - (1 - r2) / (n_ref - 2) unless
+    unbiased is false; NaN for a row without variance or observed call.  n_window[k] counts those
+    rows.  max_tiles: 128 x 128 tiles per launch (0 = default; any value gives the same bits).  The
+    event time of the kernels is kept in ctx.l2_gpu_ms."""
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    chrom = np.ascontiguousarray(chrom, dtype=np.int32)
+    bp = np.ascontiguousarray(bp, dtype=np.int64)
+    if not (rows.shape == chrom.shape == bp.shape and rows.ndim == 1):
+        raise ValueError("rows, chrom, bp: one entry per row")
+    l2 = np.zeros(max(1, len(rows)))
+    nw = np.zeros(max(1, len(rows)), dtype=np.int32)
+    ms = np.zeros(1)
+    args = _lib.L2Args(int(round(float(kb) * 1000)), 1 if unbiased else 0, int(max_tiles))
+    ctx.check(ctx.lib.dbslmm_ld_scores(ctx.h, _ptr(bed), bed.size, n_ref, len(rows), _ptr(rows), _ptr(chrom), _ptr(bp),
+                                       C.byref(args), _ptr(l2), _ptr(nw), _ptr(ms)), "ld_scores")
+    ctx.l2_gpu_ms = float(ms[0])
+    return l2[:len(rows)], nw[:len(rows)]
+
+
+def ldsc_h2(chi2, n, l2, m, intercept=None, n_blocks: int = 200, chisq_max: float = 0) -> dict:
+    """LD score regression (dbslmm_ldsc_fit; host only, no GPU): chi2 = z^2, n = the sample size per
+    SNP (or one number), l2 the LD scores, m the number of SNPs the scores stand for.  intercept None
+    = free, else fixed at that value.  Returns a dict: h2, h2_se, intercept, intercept_se, mean_chi2,
+    n (SNPs used), status (0 ok, 1 too few SNPs, 2 singular; the estimates are NaN unless 0)."""
+    chi2 = np.ascontiguousarray(chi2, dtype=np.float64)
+    l2 = np.ascontiguousarray(l2, dtype=np.float64)
+    n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, dtype=np.float64), chi2.shape))
+    if not (chi2.shape == l2.shape and chi2.ndim == 1):
+        raise ValueError("chi2, n, l2: one entry per SNP")
+    args = _lib.LdscArgs(1.0 if intercept is None else float(intercept), float(chisq_max),
+                         0 if intercept is None else 1, int(n_blocks))
+    res = _lib.LdscResult()
+    rc = _lib.load().dbslmm_ldsc_fit(len(chi2), _ptr(chi2), _ptr(n), _ptr(l2), float(m), C.byref(args), C.byref(res))
+    if rc != 0:
+        raise DbslmmError(f"ldsc_fit failed (rc={rc}): bad arguments")
+    return dict(h2=res.h2, h2_se=res.h2_se, intercept=res.intercept, intercept_se=res.intercept_se,
+                mean_chi2=res.mean_chi2, n=int(res.n_used), status=int(res.status))
 
 
 def tune_r2(scores, pheno) -> tuple[np.ndarray, int]:

@@ -22,10 +22,10 @@ EXPORTS = (
     "dbslmm_ctx_cache_bed", "dbslmm_ctx_cache_bed_fd", "dbslmm_plan_block_matrix",
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
     "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges", "dbslmm_plan_score",
-    "dbslmm_ld_r2", "dbslmm_clump",
+    "dbslmm_ld_r2", "dbslmm_clump", "dbslmm_ld_scores", "dbslmm_ldsc_fit",
 )
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
@@ -78,6 +78,24 @@ class ClumpArgs(C.Structure):
     _fields_ = [("r2", C.c_double), ("window_bp", C.c_int64)]
 
 
+class L2Args(C.Structure):
+    """dbslmm_l2_args: the window in base pairs, ldsc's adjustment on / off, tiles per launch (0 = default)."""
+    _fields_ = [("window_bp", C.c_int64), ("unbiased", C.c_int32), ("max_tiles_per_launch", C.c_int32)]
+
+
+class LdscArgs(C.Structure):
+    """dbslmm_ldsc_args: the fixed intercept (when fixed_intercept), the chi2 filter (0 = off), jackknife blocks."""
+    _fields_ = [("intercept", C.c_double), ("chisq_max", C.c_double), ("fixed_intercept", C.c_int32),
+                ("n_blocks", C.c_int32)]
+
+
+class LdscResult(C.Structure):
+    _fields_ = [("h2", C.c_double), ("h2_se", C.c_double), ("intercept", C.c_double), ("intercept_se", C.c_double),
+                ("mean_chi2", C.c_double), ("n_used", C.c_int64), ("status", C.c_int32)]
+
+
+LDSC_OK, LDSC_TOO_FEW, LDSC_SINGULAR = 0, 1, 2
+
 _lib = None
 
 
@@ -122,6 +140,8 @@ def load(path: str | None = None):
     L.dbslmm_read_snp_std.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V, V]
     L.dbslmm_ld_r2.argtypes = [V, V, C.c_int64, C.c_int32, V, C.c_int32, V]
     L.dbslmm_clump.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, P(ClumpArgs), V, V, V]
+    L.dbslmm_ld_scores.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, P(L2Args), V, V, V]
+    L.dbslmm_ldsc_fit.argtypes = [C.c_int64, V, V, V, C.c_double, P(LdscArgs), P(LdscResult)]
     L.dbslmm_valid_blocks.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V, V, V]
     L.dbslmm_plan_variance.argtypes = [V, P(TestPanel), V, V]
     L.dbslmm_plan_score.argtypes = [V, P(TestPanel), P(ScoreArgs), C.c_int32, V, V, V, V]

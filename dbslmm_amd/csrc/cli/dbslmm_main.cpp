@@ -23,6 +23,9 @@
 // are the index SNPs of PLINK's greedy clumping of the summary's significant SNPs on the reference
 // panel (software/DBSLMM.R:130-184, its `plink --clump` step on the GPU: dbslmm_clump), listed in
 // <eff>.clumped.txt; everything else is a small-effect SNP, and the run goes on as with -s / -l.
+// --ldsc --summary F1[,F2,..] -r P1[,P2,..] --out PREFIX is a mode of its own (ldsc_mode.hpp): the LD
+// scores of the panels' rows and the LD score regression of the summaries on them, i.e. the -h of
+// a solve, which the manual takes from an LDSC run (Rmd/Manual.Rmd:170).
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <sys/time.h>
@@ -72,6 +75,9 @@ struct Param {                     // PARAM, scr/dbslmm.hpp:29-45 (initialised h
     string summary;                 // --summary FILE: the whole GEMMA summary, split by clumping
     double pth = 0.0, clump_r2 = 0.2, clump_kb = 1000.0;   // --pth (plink --clump-p1), --clump-r2, --clump-kb
     bool has_pth = false;
+    bool ldsc = false;              // --ldsc: LD scores and LD score regression (ldsc_mode.hpp)
+    string out, intercept = "free"; // --out PREFIX, --intercept free|X
+    double ld_wind_kb = 1000.0, chisq_max = 0.0;   // --ld-wind-kb, --chisq-max (0 = off)
 };
 
 // The host rows keep string_views into the mmap'd input files (no per-SNP allocation).
@@ -156,13 +162,27 @@ void print_help() {
               << "                        <eff>.clumped.txt (extension)\n"
               << " --pth     [num]        --summary: significance threshold of the candidates (--clump-p1)\n"
               << " --clump-r2 [num]       --summary: r2 threshold, default 0.2\n"
-              << " --clump-kb [num]       --summary: window in kb, default 1000\n";
+              << " --clump-kb [num]       --summary: window in kb, default 1000\n"
+              << " --ldsc                 another mode: LD scores of the -r panels and the LD score regression of\n"
+              << "                        the --summary files on them (comma lists, paired in order); writes\n"
+              << "                        <out>.l2.ldscore, <out>.l2.M_5_50 and <out>.h2.txt: the -h of a solve\n"
+              << " --out     [prefix]     --ldsc: prefix of the output files\n"
+              << " --ld-wind-kb [num]     --ldsc: LD score window in kb, default 1000\n"
+              << " --intercept [free|num] --ldsc: free intercept (default) or fixed at num\n"
+              << " --chisq-max [num]      --ldsc: drop SNPs with chi2 above num (default: no filter)\n";
 }
 
 // DBSLMM::Assign (scr/dbslmm.cpp:67-172): a flag's value is skipped when it starts with '-'.
 void assign(int argc, char** argv, Param& p) {
     auto take = [&](int& i) -> const char* {
         if (i + 1 >= argc || argv[i + 1] == nullptr || argv[i + 1][0] == '-') return nullptr;
+        return argv[++i];
+    };
+    // ... but a number may be negative (the --ldsc options report it)
+    auto take_num = [&](int& i) -> const char* {
+        if (i + 1 >= argc || argv[i + 1] == nullptr) return nullptr;
+        const char* v = argv[i + 1];
+        if (v[0] == '-' && !(isdigit(static_cast<unsigned char>(v[1])) || v[1] == '.')) return nullptr;
         return argv[++i];
     };
     for (int i = 0; i < argc; ++i) {
@@ -198,6 +218,11 @@ void assign(int argc, char** argv, Param& p) {
         else if (!strcmp(a, "--pth")) { if ((v = take(i))) { p.pth = atof(v); p.has_pth = true; } }
         else if (!strcmp(a, "--clump-r2")) { if ((v = take(i))) p.clump_r2 = atof(v); }
         else if (!strcmp(a, "--clump-kb")) { if ((v = take(i))) p.clump_kb = atof(v); }
+        else if (!strcmp(a, "--ldsc")) p.ldsc = true;
+        else if (!strcmp(a, "--out")) { if ((v = take(i))) p.out = v; }
+        else if (!strcmp(a, "--ld-wind-kb")) { if ((v = take_num(i))) p.ld_wind_kb = atof(v); }
+        else if (!strcmp(a, "--intercept")) { if ((v = take_num(i))) p.intercept = v; }
+        else if (!strcmp(a, "--chisq-max")) { if ((v = take_num(i))) p.chisq_max = atof(v); }
         else if (!strcmp(a, "--dry-run")) p.dry_run = true;
         else if (!strcmp(a, "--timing")) p.timing = true;
         else if (!strcmp(a, "--repeat")) { if ((v = take(i))) p.repeat = std::max(0, atoi(v)); }
@@ -568,6 +593,8 @@ int64_t count_lines(string_view t) {
     return total + (!t.empty() && t.back() != '\n' ? 1 : 0);
 }
 
+#include "ldsc_mode.hpp"
+
 // One <eff>.txt per h2f factor (scr/dbslmm.cpp:353-364, 391-395): large rows first, then small
 // rows, "snp a1 beta beta_noscl flag"; ostream's default double format = printf %g at precision 6
 // (17 with --precise-out), produced by std::to_chars (the same digits, ~3x faster than snprintf).
@@ -674,6 +701,7 @@ int main(int argc, char** argv) {
     if (argc == 2 && argv[1][0] == '-' && argv[1][1] == 'h') { print_help(); return 0; }
     Param p;
     assign(argc, argv, p);
+    if (p.ldsc) return ldsc_mode(p);
 
     std::cout << "Options: \n-s:      " << p.s << "\n-l:      " << p.l << "\n-r:      " << p.r
               << "\n-nsnp:   " << p.nsnp << "\n-n:      " << p.n << "\n-mafMax: " << p.mafMax

@@ -1,7 +1,7 @@
 // panel_api.hip -- the entry points that read a panel beside the solve (included by plan.hip, inside
 // its extern "C" block: same translation unit): the test-set variance and polygenic scores of a
 // plan, and the context-level tools on a .bed (MAF, row statistics, standardised rows, the `valid`
-// terms, LD r2 and clumping).  Each allocates for one call on a local DevBufs (dev_bufs.hpp).
+// terms, LD r2, clumping and LD scores; the host-only LD score regression).  Each allocates for one call on a local DevBufs (dev_bufs.hpp).
 
 // "<what>: <HIP error>" as the context's error
 static int hip_fail(dbslmm_ctx* ctx, const char* what, hipError_t e) {
@@ -560,5 +560,95 @@ int dbslmm_clump(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n
     }
     const int32_t ni = clump_greedy(L, masks.data(), index_of);
     if (n_index) *n_index = ni;
+    return DBSLMM_OK;
+}
+
+// LD scores of the listed rows (ldscore.hip): the band of 128 x 128 tiles of ldsc_layout.hpp in
+// slices of at most max_tiles_per_launch tiles, dbslmm_l2_reduce after every slice.
+int dbslmm_ld_scores(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_rows,
+                     const int32_t* pos, const int32_t* chr, const int64_t* bp, const dbslmm_l2_args* args,
+                     double* l2, int32_t* n_window, double* gpu_ms) {
+    if (!ctx) return DBSLMM_E_ARG;
+    ON_FIRST_DEVICE(ctx, dbslmm_ld_scores(ctx0_, bed, bed_len, n_ref, n_rows, pos, chr, bp, args, l2, n_window, gpu_ms));
+    if (const int rc = ctx_ready(ctx)) return rc;
+    const dbslmm_l2_args a = args ? *args : dbslmm_l2_args{1000000, 1, 0};
+    ARG_CHECK(ctx, bed && n_ref > 1 && n_rows >= 0 && (n_rows == 0 || (pos && chr && bp && l2)), "bad arguments");
+    ARG_CHECK(ctx, a.window_bp >= 0, "LD score window below 0");
+    ARG_CHECK(ctx, a.max_tiles_per_launch >= 0, "max_tiles_per_launch below 0");
+    ARG_CHECK(ctx, !a.unbiased || n_ref > 2, "the unbiased LD score needs n_ref > 2");
+    if (const int rc = r2_rows_check(ctx, bed_len, n_ref, pos, n_rows)) return rc;
+    if (gpu_ms) *gpu_ms = 0.0;
+    if (n_rows == 0) return DBSLMM_OK;
+    KEY_CHECK(ctx, bed, bed_len, n_ref);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    PanelImage im;
+    hipError_t e;
+    if ((e = panel_image(ctx, bed, bed_len, n_ref, &im)) != hipSuccess) return hip_fail(ctx, "ld_scores panel image: ", e);
+    // the missing-call flags of the listed rows, from the image's row table
+    std::vector<int32_t> h_tab(static_cast<size_t>(im.n_rows) * 4);
+    if ((e = hipMemcpyAsync(h_tab.data(), im.rows(), h_tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(ctx, "ld_scores row table: ", e);
+    std::vector<uint8_t> miss(static_cast<size_t>(n_rows));
+    for (int32_t k = 0; k < n_rows; ++k) miss[static_cast<size_t>(k)] = h_tab[4 * static_cast<size_t>(pos[k]) + 2] > 0;
+    const LdscLayout L = build_ldsc_layout(n_rows, chr, bp, a.window_bp, miss.data());
+    if (n_window) ldsc_window_counts(L, n_window);
+    std::vector<int32_t> spos(static_cast<size_t>(n_rows)), schr(static_cast<size_t>(n_rows));
+    std::vector<int64_t> sbp(static_cast<size_t>(n_rows));
+    for (int32_t p = 0; p < n_rows; ++p) {
+        const int32_t k = L.order[static_cast<size_t>(p)];
+        spos[static_cast<size_t>(p)] = pos[k];
+        schr[static_cast<size_t>(p)] = chr[k];
+        sbp[static_cast<size_t>(p)] = bp[k];
+    }
+    const int32_t n_tiles = static_cast<int32_t>(L.tiles.size());
+    constexpr int32_t kDefaultSlice = (256 << 20) / (kL2SlotWords * static_cast<int32_t>(sizeof(double)));   // 131072 tiles
+    const int32_t slice = std::min(n_tiles, a.max_tiles_per_launch > 0 ? a.max_tiles_per_launch : kDefaultSlice);
+    EventPair ev;
+    DevBufs B(ctx->device);
+    int32_t *d_pos = nullptr, *d_chr = nullptr, *d_order = nullptr, *d_row_ptr = nullptr, *d_col_lo = nullptr;
+    int64_t* d_bp = nullptr;
+    L2Tile* d_tiles = nullptr;
+    double *d_slots = nullptr, *d_run = nullptr, *d_out = nullptr;
+    if ((e = B.upload(&d_pos, spos, st)) != hipSuccess || (e = B.upload(&d_chr, schr, st)) != hipSuccess ||
+        (e = B.upload(&d_bp, sbp, st)) != hipSuccess || (e = B.upload(&d_order, L.order, st)) != hipSuccess ||
+        (e = B.upload(&d_row_ptr, L.row_ptr, st)) != hipSuccess || (e = B.upload(&d_col_lo, L.col_lo, st)) != hipSuccess ||
+        (e = B.upload(&d_tiles, L.tiles, st)) != hipSuccess ||
+        (e = B.alloc(&d_slots, static_cast<size_t>(slice) * kL2SlotWords)) != hipSuccess ||
+        (e = B.zeroed(&d_run, static_cast<size_t>(n_rows), st)) != hipSuccess ||
+        (e = B.alloc(&d_out, static_cast<size_t>(n_rows))) != hipSuccess ||
+        (e = ev.create()) != hipSuccess || (e = hipEventRecord(ev.ev0, st)) != hipSuccess)
+        return hip_fail(ctx, "ld_scores alloc/upload: ", e);
+    const int64_t kpad = im.pitch * 4;
+    for (int32_t t0 = 0; t0 < n_tiles; t0 += slice) {
+        const int32_t t1 = std::min(n_tiles, t0 + slice);
+        hipLaunchKernelGGL(dbslmm_l2_tiles, dim3(static_cast<unsigned>(t1 - t0)), dim3(256), gram::kLdsBytes, st,
+                           im.mem.get(), kpad, im.rows(), im.n_rows, n_ref, d_pos, n_rows, d_tiles + t0, t1 - t0, d_chr,
+                           d_bp, a.window_bp, a.unbiased, d_slots);
+        hipLaunchKernelGGL(dbslmm_l2_reduce, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, st, d_slots,
+                           t0, t1, d_row_ptr, d_col_lo, n_rows, d_run, t1 == n_tiles ? 1 : 0, im.rows(), d_pos, n_ref,
+                           d_order, d_out);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, "ld_scores launch: ", e);
+    }
+    float ms = 0.0f;
+    if ((e = hipEventRecord(ev.ev1, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(l2, d_out, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev.ev0, ev.ev1)) != hipSuccess)
+        return hip_fail(ctx, "ld_scores run: ", e);
+    if (gpu_ms) *gpu_ms = ms;
+    return DBSLMM_OK;
+}
+
+// LD score regression (ldsc_fit.hpp): host only.
+int dbslmm_ldsc_fit(int64_t n, const double* chi2, const double* n_obs, const double* l2, double m,
+                    const dbslmm_ldsc_args* args, dbslmm_ldsc_result* out) {
+    const dbslmm_ldsc_args a = args ? *args : dbslmm_ldsc_args{1.0, 0.0, 0, 0};
+    if (!out || n < 0 || (n > 0 && (!chi2 || !n_obs || !l2)) || !(m > 0.0) || a.n_blocks < 0 || a.n_blocks == 1 ||
+        !(a.chisq_max >= 0.0))
+        return DBSLMM_E_ARG;
+    const ldsc::Result r = ldsc::fit(n, chi2, n_obs, l2, m, a.fixed_intercept != 0, a.intercept,
+                                     a.n_blocks > 0 ? a.n_blocks : 200, a.chisq_max);
+    *out = dbslmm_ldsc_result{r.h2, r.h2_se, r.intercept, r.intercept_se, r.mean_chi2, r.n_used, r.status};
     return DBSLMM_OK;
 }

@@ -40,6 +40,7 @@
 
 #include "../../include/dbslmm_hip.h"
 #include "dev_bufs.hpp"
+#include "ldsc_fit.hpp"
 #include "out_ranges.hpp"
 #include "plan_layout.hpp"
 
@@ -52,6 +53,7 @@
 #include "trsv.hip"
 #include "pcg.hip"
 #include "clump.hip"
+#include "ldscore.hip"
 
 namespace {
 // the instants of a timed run, one event each (collect_timing turns them into kernel spans)
@@ -670,6 +672,8 @@ int dbslmm_ctx_create(int device, dbslmm_ctx** out) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize,
                                 static_cast<int>(kCholChebLds)) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(dbslmm_gram_big),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, gram::kLdsBytes) == hipSuccess &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(dbslmm_l2_tiles),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, gram::kLdsBytes) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void*>(dbslmm_gram_huge),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, gram::kHLdsBytes) == hipSuccess &&

@@ -14,6 +14,8 @@
  *                         reference SNP, maf only.
  *   dbslmm_clump          the large-effect clumping of software/DBSLMM.R:139-145 (`plink --clump` on
  *                         the reference panel): the index SNPs of a candidate list.
+ *   dbslmm_ld_scores,     the heritability the reference takes from an LDSC run (Rmd/Manual.Rmd:170):
+ *   dbslmm_ldsc_fit       LD scores of the reference panel and the LD score regression.
  *   dbslmm_read_snp_std   IO::readSNPIm + SNPPROC::nomalizeVec (dtpr.cpp:285-364, 375-380) for a
  *                         list of bed rows: standardised fp64 columns (parity / diagnostics).
  *
@@ -33,7 +35,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 20
+#define DBSLMM_ABI_VERSION 21
 
 enum {
     DBSLMM_OK = 0,
@@ -523,6 +525,46 @@ typedef struct dbslmm_clump_args { double r2; int64_t window_bp; } dbslmm_clump_
 int dbslmm_clump(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_cand,
                  const int32_t* pos, const int32_t* chr, const int64_t* bp,
                  const dbslmm_clump_args* args, int32_t* index_of, int32_t* n_index, double* gpu_ms);
+
+/* LD scores (ABI 21; ldscore.hip): what the reference's manual leaves to LDSC (Rmd/Manual.Rmd:170).
+ * The listed rows -- bed row pos[k], chromosome code chr[k] (any integer per chromosome), base pair
+ * bp[k] -- come in any order and may repeat.  window_bp >= 0.
+ *   l2[k] = sum over the listed j with chr[j] == chr[k] and |bp[j] - bp[k]| <= window_bp (j = k
+ *           included) of t_kj
+ * r2_kj is exactly dbslmm_ld_r2's quantity (missing calls at the row mean, n = n_ref).  With
+ * unbiased != 0 (args == NULL: unbiased, window 1 Mb) t = r2 - (1 - r2) / (n_ref - 2), ldsc's
+ * adjustment, which needs n_ref > 2 (else DBSLMM_E_ARG); with unbiased == 0 t = r2.  A row whose r2
+ * is NaN (no variance or no observed call) gets l2 = NaN and contributes nothing to any other row.
+ * n_window[k] (optional) = the number of listed j inside the window of k, k itself and NaN rows
+ * included: a pure position count.  gpu_ms (optional) = event time of the tile and reduce kernels.
+ * The tile list is processed in slices of at most max_tiles_per_launch 128 x 128 tiles (0 = the
+ * default, which keeps the partial-sum buffer at 256 MiB); l2 is bit-identical for every slice
+ * size and from run to run (no atomics; the order is fixed, ldscore.hip).  The n_ref cap is the FP4
+ * Gram's (dbslmm_ld_r2); n_rows == 0 is valid and n_rows has no 8192 limit.  Panel-key rules of
+ * dbslmm_bed_maf; a multi-device context answers from its first device. */
+typedef struct dbslmm_l2_args { int64_t window_bp; int32_t unbiased; int32_t max_tiles_per_launch; } dbslmm_l2_args;
+int dbslmm_ld_scores(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_ref, int32_t n_rows,
+                     const int32_t* pos, const int32_t* chr, const int64_t* bp, const dbslmm_l2_args* args,
+                     double* l2, int32_t* n_window, double* gpu_ms);
+
+/* LD score regression (ABI 21; ldsc_fit.hpp, which states the rule in full).  Host-only: no context,
+ * no GPU.  chi2[j] = z_j^2, n_obs[j] = N_j, l2[j] the LD score of SNP j < n (all finite), m = the
+ * number of SNPs the LD scores stand for.  fixed_intercept != 0 holds the intercept at `intercept`;
+ * n_blocks = jackknife blocks (0 = 200; else >= 2); chisq_max > 0 drops the SNPs with chi2 above it
+ * first (0 = off: no filter by default).  args == NULL: free intercept and the defaults.
+ * Returns DBSLMM_E_ARG for null arrays, m <= 0 or n_blocks == 1 or < 0; else DBSLMM_OK with
+ * out->status: DBSLMM_LDSC_OK, DBSLMM_LDSC_TOO_FEW (fewer SNPs than twice the parameters) or
+ * DBSLMM_LDSC_SINGULAR (normal equations of the fit or of a delete-one block; e.g. every x equal
+ * with a free intercept); the estimates are NaN unless OK.  intercept_se is 0 when fixed. */
+enum { DBSLMM_LDSC_OK = 0, DBSLMM_LDSC_TOO_FEW = 1, DBSLMM_LDSC_SINGULAR = 2 };
+typedef struct dbslmm_ldsc_args { double intercept; double chisq_max; int32_t fixed_intercept; int32_t n_blocks; } dbslmm_ldsc_args;
+typedef struct dbslmm_ldsc_result {
+    double h2, h2_se, intercept, intercept_se, mean_chi2;
+    int64_t n_used;
+    int32_t status;
+} dbslmm_ldsc_result;
+int dbslmm_ldsc_fit(int64_t n, const double* chi2, const double* n_obs, const double* l2, double m,
+                    const dbslmm_ldsc_args* args, dbslmm_ldsc_result* out);
 
 /* readSNPIm + nomalizeVec for rows pos[0..n_rows): out is n_ref x n_rows column-major fp64
  * (column j = standardised dosages of bed row pos[j]); maf (optional) n_rows entries. */
