@@ -141,10 +141,10 @@ def _edge_panel(n_ref):
 
 
 @gpu
-@pytest.mark.parametrize("n_ref", [3, 255, 256, 257, 400, 4097])
+@pytest.mark.parametrize("n_ref", [3, 255, 256, 257, 400, 513, 769, 4097])
 def test_ld_r2_shape_edges(n_ref):
     """n_rows 1, 31, 32, 33, 64, 65 at every n_ref (pad individuals, pad bits, kpad steps 256 / 512 /
-    4352): a list without a missing call (raw tiles) and one with (four-product tiles), each holding
+    768 / 1024 / 4352): a list without a missing call (raw tiles) and one with (four-product tiles), each holding
     flipped rows, a monomorphic row and, the second, an all-missing row and one without variance:
     NaN row, column and diagonal."""
     from dbslmm_amd import ld_r2

@@ -52,11 +52,12 @@ def _ctx():
     return Context(0)
 
 
-def l2_bar(ref: dict, X, chrom, bp, unbiased, n_ref, fpbar=None):
+def l2_bar(ref: dict, X, chrom, bp, unbiased, n_ref, fpbar=None, fp=None):
     """(Bar per row, four-product pair mask) of the module docstring; fpbar: four_product_bar of
-    every pair of X when the caller already has it"""
-    nmiss = (np.asarray(X) < 0).sum(axis=1)
-    fp = LR.four_product_pairs128(nmiss, chrom, bp)
+    every pair of X when the caller already has it; fp: the four-product pair mask when the rows are
+    part of a longer list (the tiles are those of the whole call's position order)"""
+    if fp is None:
+        fp = LR.four_product_pairs128((np.asarray(X) < 0).sum(axis=1), chrom, bp)
     r2, t, used = ref["r2"], ref["t"], ref["used"]
     with np.errstate(invalid="ignore"):
         rbar = 4 * np.spacing(np.abs(r2.astype(np.float64))).astype(LD)
@@ -123,13 +124,16 @@ def _sub(r2, fpbar, n):
 
 
 @gpu
-@pytest.mark.parametrize("n_ref,with_missing", [(3, False)] + [(n, m) for n in (255, 256, 257, 400, 4097) for m in (False, True)])
+@pytest.mark.parametrize("n_ref,with_missing", [(3, False)] + [(n, m) for n in (255, 256, 257, 400, 4097) for m in (False, True)] +
+                         [(513, False), (769, False)])
 def test_ld_scores_shape_edges(n_ref, with_missing):
     """n_rows 1, 127, 128, 129, 256, 257, 300 at every n_ref (pad individuals, pad bits, kpad 256 / 512 /
-    4352; one, two and three tile rows, whole and partial), rows 1 kb apart under a 150 kb window (a band
-    two tile columns wide at 300 rows), with and without ldsc's adjustment.  Without missing calls every
-    tile is raw; with them the 300-row list mixes raw tile (0, 0) with four-product tiles.  n_ref = 3
-    (n - 2 = 1) runs on the raw list only: unbiased = 0, plus one call with the adjustment."""
+    4352, and 768 / 1024 on the raw list: 1, 2, 17, 3 and 4 K stages of 256 individuals -- 3 is odd with
+    one load ahead only, 4 the smallest even count that loads stage st + 3; one, two and three tile
+    rows, whole and partial), rows 1 kb apart under a 150 kb window (a band two tile columns wide at
+    300 rows), with and without ldsc's adjustment.  Without missing calls every tile is raw; with them
+    the 300-row list mixes raw tile (0, 0) with four-product tiles.  n_ref = 3 (n - 2 = 1) runs on the
+    raw list only: unbiased = 0, plus one call with the adjustment."""
     from dbslmm_amd import ld_r2, ld_scores
     bed, X, r2, fpbar = _edge_panel(n_ref, with_missing)
     worst = {}
@@ -234,6 +238,99 @@ def test_ld_scores_slices_and_repeats_give_the_same_bytes():
         got, nw2 = ld_scores(_ctx(), bed, n_ref, rows, chrom, bp, kb=window_bp / 1000, max_tiles=mt)
         assert got.tobytes() == base.tobytes(), mt
         np.testing.assert_array_equal(nw2, nw)
+
+
+# ------------------------------------------------------------------------------------------------
+# a ragged band: the tile rows reach 0, 1, 2 and 3 tile columns past the diagonal, up and down
+# ------------------------------------------------------------------------------------------------
+RAGGED_N, RAGGED_WINDOW = 900, 100_000
+
+
+def _ragged_bp():
+    """bp of 900 positions (8 tile rows, the last one 4 positions): stretches 900, 240, 1500 and 800 bp
+    apart (111, 416, 66 and 125 rows inside a 100 kb window) and 500 kb of nothing between positions 599 and 600 (inside tile row 4) and 300 kb after position 639 (where it ends)"""
+    d = np.zeros(RAGGED_N, dtype=np.int64)
+    for a, b, step in ((0, 200, 900), (200, 520, 240), (520, 640, 1500), (640, RAGGED_N, 800)):
+        d[a:b] = step
+    d[600], d[640] = 500_000, 300_000
+    return np.cumsum(d)
+
+
+def _ragged_two_chromosomes():
+    """the same rows, positions 450.. on a second chromosome whose bp start again: the change falls
+    inside tile row 3 (positions 384..511)"""
+    bp = _ragged_bp()
+    chrom = np.where(np.arange(RAGGED_N) < 450, 1, 2)
+    return chrom, np.where(chrom == 1, bp, bp - bp[450] + 1000)
+
+
+RAGGED_CASES = {
+    # name: (chrom, bp, reach of every tile row: hi(last p of I) / 128 - I)
+    "one chromosome": (np.ones(RAGGED_N, dtype=np.int64), _ragged_bp(), [2, 3, 2, 1, 0, 1, 1, 0]),
+    "two chromosomes, the change inside a tile": _ragged_two_chromosomes() + ([2, 2, 1, 1, 0, 1, 1, 0],),
+}
+RAGGED_MISSING = (380, 520)        # caller rows (= positions) with missing calls: tile rows 2, 3 and 4
+
+
+def tile_row_reach(chrom, bp, window_bp):
+    """per tile row I of the position order, the tile columns its last position's window reaches past
+    the diagonal: from the oracle's order and window matrix alone"""
+    order = LR.position_order(chrom, bp)
+    W = LR.window_matrix(chrom, bp, window_bp)[np.ix_(order, order)]
+    n = len(order)
+    return [int(np.flatnonzero(W[min(n, 128 * (I + 1)) - 1]).max()) // 128 - I for I in range((n + 127) // 128)]
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_panel():
+    """900 rows at n_ref 400 in LD runs of 4; rows 380..519 carry 8 % missing calls, one of them all
+    missing; a monomorphic row among the others; flipped rows.  bed, X, r2, four-product bars."""
+    n_ref = 400
+    rng = np.random.default_rng(77)
+    X = _rows(rng, RAGGED_N, n_ref)
+    sub = X[RAGGED_MISSING[0]:RAGGED_MISSING[1]]
+    sub[rng.random(sub.shape) < 0.08] = -1
+    X[400] = -1                                    # all missing
+    X[50] = 2                                      # monomorphic, in a raw tile
+    bed = flip_alleles(CR.encode(X), n_ref, np.arange(1, RAGGED_N, 3))
+    X = CR.decode(bed, n_ref, np.arange(RAGGED_N))
+    X.setflags(write=False)
+    r2 = CR.r2_longdouble(X)
+    return bed, X, r2, four_product_bar(X, r2)
+
+
+@gpu
+@pytest.mark.parametrize("name", list(RAGGED_CASES))
+def test_ld_scores_ragged_band(name):
+    """dbslmm_l2_reduce finds tile (I, P) at row_ptr[I] + (P - I) and starts at col_lo[P]: a band whose
+    width changes from tile row to tile row (tests/test_ldsc_host.py asserts the reaches from the
+    positions alone), raw and four-product tiles in it.  Every row at its bar with and without the
+    adjustment, n_window exact, and the bytes of the whole launch for slices of 1, 5 and 7 tiles and
+    for a shuffled caller order."""
+    from dbslmm_amd import ld_scores
+    n_ref = 400
+    bed, X, r2, fpbar = _ragged_panel()
+    chrom, bp, _ = RAGGED_CASES[name]
+    chrom, bp = chrom.astype(np.int32), bp.astype(np.int64)
+    rows = np.arange(RAGGED_N, dtype=np.int32)
+    base = {}
+    for unbiased in (True, False):
+        got, nw = ld_scores(_ctx(), bed, n_ref, rows, chrom, bp, kb=RAGGED_WINDOW / 1000, unbiased=unbiased)
+        _, _, worst = check_l2(got, nw, X, chrom, bp, RAGGED_WINDOW, unbiased, n_ref, f"ragged, {name}, unbiased {unbiased}",
+                               r2, fpbar)
+        assert set(worst) == {"raw", "four-product"}
+        assert np.isnan(got[50]) and np.isnan(got[400]) and int(np.isnan(got).sum()) == 2
+        base[unbiased] = (got, nw)
+    got, nw = base[True]
+    for mt in (1, 5, 7, 0):
+        g2, nw2 = ld_scores(_ctx(), bed, n_ref, rows, chrom, bp, kb=RAGGED_WINDOW / 1000, max_tiles=mt)
+        assert g2.tobytes() == got.tobytes(), mt
+        np.testing.assert_array_equal(nw2, nw)
+    perm = np.random.default_rng(9).permutation(RAGGED_N)
+    for mt in (0, 5):
+        g3, nw3 = ld_scores(_ctx(), bed, n_ref, rows[perm], chrom[perm], bp[perm], kb=RAGGED_WINDOW / 1000, max_tiles=mt)
+        assert g3.tobytes() == got[perm].tobytes(), mt
+        np.testing.assert_array_equal(nw3, nw[perm])
 
 
 @gpu

@@ -101,6 +101,40 @@ def test_gpu_window_cases_have_the_band_widths_they_claim():
     assert np.max(np.diff(np.sort(bp))) > w
 
 
+def test_gpu_ragged_cases_have_the_reaches_they_claim():
+    """the ragged band of tests/test_ldsc.py from the oracle's position order and window matrix alone:
+    the tile rows reach 0, 1, 2 and 3 tile columns past the diagonal, neither rising nor falling
+    throughout; distinct positions (the shuffled call has one position order); a gap wider than the
+    window and none of its pairs in any window; dense and sparse stretches; the rows with missing calls
+    cover a whole tile row and leave others untouched; the second case changes chromosome inside a tile
+    and no window crosses the change"""
+    from test_ldsc import RAGGED_CASES, RAGGED_MISSING, RAGGED_N, RAGGED_WINDOW, tile_row_reach
+    for name, (chrom, bp, reach) in RAGGED_CASES.items():
+        got = tile_row_reach(chrom, bp, RAGGED_WINDOW)
+        assert got == reach, (name, got)
+        d = np.diff(got)
+        assert (d > 0).any() and (d < 0).any(), name
+        assert len(chrom) == RAGGED_N == 900 and len(got) == 8
+        order = LR.position_order(chrom, bp)
+        np.testing.assert_array_equal(order, np.arange(RAGGED_N))          # caller order = position order
+        assert len({(int(c), int(b)) for c, b in zip(chrom, bp)}) == RAGGED_N
+        nw = LR.window_matrix(chrom, bp, RAGGED_WINDOW).sum(axis=1)
+        assert nw.min() < 80 and nw.max() > 400, (name, nw.min(), nw.max())  # sparse and dense stretches
+    chrom, bp, reach = RAGGED_CASES["one chromosome"]
+    assert set(reach) == {0, 1, 2, 3}
+    gap = int(np.argmax(np.diff(bp)))
+    assert bp[gap + 1] - bp[gap] > RAGGED_WINDOW and gap // 128 == (gap + 1) // 128   # the gap inside tile row 4
+    assert not LR.window_matrix(chrom, bp, RAGGED_WINDOW)[:gap + 1, gap + 1:].any()
+    chrom, bp, _ = RAGGED_CASES["two chromosomes, the change inside a tile"]
+    change = int(np.flatnonzero(np.diff(chrom))[0]) + 1
+    assert len(np.flatnonzero(np.diff(chrom))) == 1 and change % 128 != 0
+    assert not LR.window_matrix(chrom, bp, RAGGED_WINDOW)[:change, change:].any()
+    assert bp[chrom == 2].min() < bp[chrom == 1].max()               # the bp ranges of the two overlap
+    lo, hi = RAGGED_MISSING
+    assert hi - lo >= 128 and any(lo <= 128 * I and 128 * (I + 1) <= hi for I in range(8))
+    assert lo // 128 > 0 and (hi - 1) // 128 < 5                     # tile rows 0, 1, 5, 6, 7 hold no missing call
+
+
 def test_ldsc_layout_and_fit_under_asan_ubsan():
     """tests/host/ldsc_check.cpp: the 128-band layout from first principles and ldsc_fit.hpp on a fixed
     data set, under ASan + UBSan (a stand-alone program: no preloaded runtime)"""
