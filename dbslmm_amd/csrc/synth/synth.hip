@@ -93,11 +93,15 @@ extern "C" int dbslmm_synth_bed(int device, int32_t num_block, const int64_t* bl
         snprintf(g_err, sizeof(g_err), "bad argument");
         return -1;
     }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail("hipSetDevice", e);
-    const int64_t m = blk_ptr[num_block], nb = (n_ref + 3) / 4;
+    // the kernel writes rows blk_ptr[0] .. blk_ptr[num_block] - 1 and nothing else: a start below 0
+    // or a falling entry would send it outside the image
+    if (blk_ptr[0] < 0) { snprintf(g_err, sizeof(g_err), "blk_ptr starts below 0"); return -1; }
     for (int b = 0; b < num_block; ++b)
         if (blk_ptr[b + 1] < blk_ptr[b]) { snprintf(g_err, sizeof(g_err), "blk_ptr not monotone"); return -1; }
+    const int64_t lo = blk_ptr[0], m = blk_ptr[num_block], nb = (n_ref + 3) / 4;
+    if (m == lo) return 0;                                  // every block empty: nothing to write
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail("hipSetDevice", e);
     int64_t* d_ptr = nullptr;
     float* d_thr = nullptr;
     uint8_t* d_out = nullptr;
@@ -109,11 +113,13 @@ extern "C" int dbslmm_synth_bed(int device, int32_t num_block, const int64_t* bl
     } else if ((e = hipMemcpy(d_ptr, blk_ptr, (num_block + 1) * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess ||
                (e = hipMemcpy(d_thr, thr, m * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
         rc = fail("hipMemcpy H2D", e);
-    } else if (m > 0) {
+    } else {
         dim3 grid((unsigned)((nb + 255) / 256), (unsigned)num_block);
         synth_panel<<<grid, 256>>>(d_ptr, d_thr, d_out, n_ref, nb, seed, rho, miss_rate);
+        // rows below blk_ptr[0] were never generated: they stay the caller's
         if ((e = hipGetLastError()) != hipSuccess) rc = fail("synth_panel launch", e);
-        else if ((e = hipMemcpy(rows, d_out, m * nb, hipMemcpyDeviceToHost)) != hipSuccess) rc = fail("hipMemcpy D2H", e);
+        else if ((e = hipMemcpy(rows + lo * nb, d_out + lo * nb, (m - lo) * nb, hipMemcpyDeviceToHost)) != hipSuccess)
+            rc = fail("hipMemcpy D2H", e);
     }
     (void)hipFree(d_ptr);
     (void)hipFree(d_thr);
