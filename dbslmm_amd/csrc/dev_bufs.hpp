@@ -1,4 +1,5 @@
-// dev_bufs.hpp -- the one owner of device allocations.  A DevBufs records every pointer it hands
+// dev_bufs.hpp -- the owners of HIP resources: DevBufs for device allocations, and below it the
+// host-side ones (PinnedBuf, EventList, GraphExecs).  A DevBufs records every pointer it hands
 // out and frees what is left when it goes: a plan keeps one for its d_* members, an entry point
 // that allocates for one call keeps a local one.  No policy beyond that: every call is one
 // hipMalloc / hipFree (nothing pooled or kept between calls).
@@ -7,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 class DevBufs {
@@ -78,18 +80,67 @@ private:
     }
 };
 
-// The two timing events around one call's kernels, destroyed with the scope.
-struct EventPair {
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    EventPair() = default;
-    EventPair(const EventPair&) = delete;
-    EventPair& operator=(const EventPair&) = delete;
-    ~EventPair() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
+// A pinned host buffer that only grows: reserve(bytes) frees and allocates again only for a larger
+// size (contents are not kept), with the flags given once.  Freed with its owner.
+class PinnedBuf {
+public:
+    explicit PinnedBuf(unsigned flags = hipHostMallocDefault) : flags_(flags) {}
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { (void)drop(); }
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= bytes_) return hipSuccess;
+        hipError_t e = drop();
+        if (e == hipSuccess && (e = hipHostMalloc(&p_, bytes, flags_)) == hipSuccess) bytes_ = bytes;
+        return e;
     }
-    hipError_t create() {
-        const hipError_t e = hipEventCreate(&ev0);
-        return e != hipSuccess ? e : hipEventCreate(&ev1);
+    template <typename T = void>
+    T* get() const { return static_cast<T*>(p_); }
+
+private:
+    void* p_ = nullptr;
+    size_t bytes_ = 0;
+    unsigned flags_;
+    hipError_t drop() {
+        void* old = std::exchange(p_, nullptr);
+        bytes_ = 0;
+        return old ? hipHostFree(old) : hipSuccess;
+    }
+};
+
+// A list of events that grows on demand (each created with the list's flags), and a list of
+// instantiated graphs (null = not captured yet); reset() destroys what they hold.
+struct EventList {
+    std::vector<hipEvent_t> ev;
+    unsigned flags;
+    explicit EventList(unsigned fl = hipEventDisableTiming) : flags(fl) {}
+    EventList(const EventList&) = delete;
+    EventList& operator=(const EventList&) = delete;
+    ~EventList() { reset(); }
+    hipError_t grow(size_t n) {   // at least n events
+        hipError_t rc = hipSuccess;
+        for (hipEvent_t e; ev.size() < n && (rc = hipEventCreateWithFlags(&e, flags)) == hipSuccess;) ev.push_back(e);
+        return rc;
+    }
+    hipEvent_t operator[](size_t i) const { return ev[i]; }
+    void reset() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        ev.clear();
+    }
+};
+struct GraphExecs {
+    std::vector<hipGraphExec_t> gx;
+    GraphExecs() = default;
+    GraphExecs(const GraphExecs&) = delete;
+    GraphExecs& operator=(const GraphExecs&) = delete;
+    ~GraphExecs() { reset(); }
+    hipGraphExec_t& at(size_t i) {   // slot i (null until a graph is instantiated into it)
+        if (gx.size() <= i) gx.resize(i + 1, nullptr);
+        return gx[i];
+    }
+    void reset() {
+        for (hipGraphExec_t g : gx)
+            if (g) (void)hipGraphExecDestroy(g);
+        gx.clear();
     }
 };

@@ -335,7 +335,7 @@ static void plan_units_pcg(int32_t nb, const int32_t* m, const int32_t* ml, int3
 }
 }  // namespace shard
 
-// Does a plan of this problem take the PCG route for these sigmas?  (plan.hip pcg_route at the
+// Does a plan of this problem take the PCG route for these sigmas?  (route_pcg.hip pcg_route at the
 // problem level: the same options, tau, large-SNP and prior-shift rules.)
 static bool problem_pcg_route(const dbslmm_problem* pr, const double* sig, int n, bool has_large) {
     const dbslmm_options* o = pr->opts;
@@ -543,7 +543,6 @@ static int mp_build(dbslmm_ctx* ctx, const dbslmm_problem* pr, int32_t K, const 
     if (rc != DBSLMM_OK) { dbslmm_plan_destroy(p); return rc; }
     // jobs without blocks hold no plan: dropped
     J.erase(std::remove_if(J.begin(), J.end(), [](const DeviceShard& s) { return s.plan == nullptr; }), J.end());
-    p->ran = false;
     *out = p;
     return DBSLMM_OK;
 }
@@ -592,7 +591,7 @@ static int mp_download(dbslmm_plan* p, int copy, double* beta_s, double* beta_l,
         if (jc < 0) return DBSLMM_OK;
         std::vector<double> bs(sh.s_idx.size()), bl(sh.l_idx.size());
         std::vector<int32_t> st(sh.blocks.size());
-        const int rc = download_copy(sh.plan, jc, bs.data(), bl.data(), st.data());
+        const int rc = download_copies(sh.plan, jc, 1, bs.data(), bl.data(), st.data());
         if (rc != DBSLMM_OK) return rc;
         if (beta_s) for (size_t i = 0; i < bs.size(); ++i) beta_s[sh.s_idx[i]] = bs[i];
         if (beta_l) for (size_t i = 0; i < bl.size(); ++i) beta_l[sh.l_idx[i]] = bl[i];
@@ -664,11 +663,13 @@ static int mp_run(dbslmm_plan* p, const double* sigmas, int n, bool wait) {
         return r;
     });
     if (rc == DBSLMM_OK) {
-        p->ran = true;
-        p->stopped = false;
-        p->var_copy = n - 1;
-        p->sigma_run = sigmas[n - 1];
-        p->score_copies = n;
+        LastRun r = p->last;   // (pcg_*, cheb_*, cg_ran, score_stale are the jobs' facts: kept, at their defaults here)
+        r.ran = true;
+        r.stopped = false;
+        r.var_copy = n - 1;
+        r.sigma_run = sigmas[n - 1];
+        r.score_copies = n;
+        close_run(p, r);
     }
     return rc;
 }
@@ -710,11 +711,11 @@ static int mp_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* diag
     auto& S = p->mp->shards;
     if (!p->mp->partial) std::fill(diags, diags + static_cast<size_t>(n_test) * p->num_block, 0.0);
     // the jobs holding the last solve's factorisation (the caller's copy var_copy is their last)
-    auto holds = [&](const DeviceShard& sh) { return !sh.run_copies.empty() && sh.run_copies.back() == p->var_copy; };
+    auto holds = [&](const DeviceShard& sh) { return !sh.run_copies.empty() && sh.run_copies.back() == p->last.var_copy; };
     // every job's pending single-sigma re-run (graph captures) first, drained, then the variances
     const int rc0 = fan_out(p, [&](int d) -> int {
         dbslmm_plan* q = S[d].plan;
-        if (!holds(S[d]) || !q->cheb_pending_var) return DBSLMM_OK;
+        if (!holds(S[d]) || !q->last.cheb_pending_var) return DBSLMM_OK;
         const int r = variance_factor(q);
         return r == DBSLMM_OK ? dbslmm_plan_sync(q) : r;
     });

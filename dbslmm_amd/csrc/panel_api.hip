@@ -15,10 +15,12 @@ static int hip_fail(dbslmm_ctx* ctx, const char* what, hipError_t e) {
 // so no shard captures a graph while another runs the variance's synchronous calls.
 static int variance_factor(dbslmm_plan* p) {
     if (const int rc = pcg_finish(p)) return rc;
-    if (!p->cheb_pending_var && !p->pcg_pending_var) return DBSLMM_OK;
-    const double sg = p->sigma_run;
-    p->cheb_pending_var = false;
-    p->pcg_pending_var = false;
+    if (!p->last.cheb_pending_var && !p->last.pcg_pending_var) return DBSLMM_OK;
+    const double sg = p->last.sigma_run;
+    LastRun r = p->last;   // (cleared even if the re-solve below fails: it is not tried twice)
+    r.cheb_pending_var = false;
+    r.pcg_pending_var = false;
+    close_run(p, r);
     p->force_factor = true;          // the variance needs the factor of this sigma
     const int rc = run_impl(p, &sg, 1);
     p->force_factor = false;
@@ -75,8 +77,8 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
                          int32_t* n_test_out) {
     if (!p) return DBSLMM_E_ARG;
     dbslmm_ctx* ctx = p->ctx;
-    if (!p->ran) { ctx->err = "plan_variance before plan_run"; return DBSLMM_E_STATE; }
-    if (p->stopped) { ctx->err = "plan_variance after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
+    if (!p->last.ran) { ctx->err = "plan_variance before plan_run"; return DBSLMM_E_STATE; }
+    if (p->last.stopped) { ctx->err = "plan_variance after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
     if (p->mp) return mp_variance(p, tp, diags, n_test_out);
     ARG_CHECK(ctx, tp && tp->bed && tp->indicator && tp->n_total > 0, "bad test panel");
     if (const int rc = variance_factor(p)) return rc;
@@ -114,11 +116,11 @@ int dbslmm_plan_variance(dbslmm_plan* p, const dbslmm_test_panel* tp, double* di
                            dim3(256), 0, st, d_tbed, T.tbps, d_tpos, p->n_slots, d_sel, n_test, cpitch, d_cbed);
         hipLaunchKernelGGL(dbslmm_snp_stats, dim3(static_cast<unsigned>((p->n_slots + 3) / 4)), dim3(256), 0,
                            st, d_cbed, n_test, cpitch, d_cpos, p->n_slots, d_mu, d_rsd);
+        const CopyView fv = copy_view(p, p->last.var_copy);   // the copy holding the latest factorisation
         hipLaunchKernelGGL(dbslmm_variance, dim3(static_cast<unsigned>(nt_pad / 64), p->n_nonempty),
-                           dim3(256), 0, st, p->d_M + p->var_copy * p->M_elems, p->d_row0, p->d_m,
-                           p->d_ms, p->d_ld, p->d_matoff, p->d_blk_id, p->d_status + p->var_copy * p->nbk,
+                           dim3(256), 0, st, fv.M, p->d_row0, p->d_m, p->d_ms, p->d_ld, p->d_matoff, p->d_blk_id, fv.status,
                            d_cbed, cpitch, d_mu, d_rsd, n_test,
-                           p->sigma_run, static_cast<double>(p->n_obs), d_Y, nt_pad, d_diags);
+                           p->last.sigma_run, static_cast<double>(p->n_obs), d_Y, nt_pad, d_diags);
     }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess ||
         (e = hipMemcpy(diags, d_diags, ndiag * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
@@ -135,25 +137,22 @@ int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_
                       double* gpu_ms) {
     if (!p) return DBSLMM_E_ARG;
     dbslmm_ctx* ctx = p->ctx;
-    if (!p->ran) { ctx->err = "plan_score before plan_run"; return DBSLMM_E_STATE; }
-    if (p->stopped) { ctx->err = "plan_score after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
+    if (!p->last.ran) { ctx->err = "plan_score before plan_run"; return DBSLMM_E_STATE; }
+    if (p->last.stopped) { ctx->err = "plan_score after a run stopped at the Gram (debug_stop)"; return DBSLMM_E_STATE; }
     ARG_CHECK(ctx, tp && tp->bed && tp->n_total > 0, "bad test panel");
     const int32_t mode = args ? args->mode : DBSLMM_SCORE_COUNTS;
     ARG_CHECK(ctx, mode == DBSLMM_SCORE_COUNTS || mode == DBSLMM_SCORE_STD, "score mode");
     ARG_CHECK(ctx, !args || args->chunk_slots >= 0, "chunk_slots must be >= 0");
-    ARG_CHECK(ctx, n_copies == p->score_copies, "n_copies must equal the copies of the latest run");
+    ARG_CHECK(ctx, n_copies == p->last.score_copies, "n_copies must equal the copies of the latest run");
     ARG_CHECK(ctx, p->n_s == 0 || tp->s_pos, "test panel s_pos missing");
     ARG_CHECK(ctx, p->n_l == 0 || tp->l_pos, "test panel l_pos missing");
     if (p->mp) return mp_score(p, tp, args, n_copies, scores, dropped, n_test_out, gpu_ms);
-    if (p->score_stale) {
+    if (p->last.score_stale) {
         ctx->err = "plan_score after plan_variance re-solved the latest sigma (the device results of copy 0 are "
                    "overwritten): score before the variance, or run again";
         return DBSLMM_E_STATE;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (const int rc = pcg_finish(p)) return rc;       // a run still pending
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (const int rc = check_trsv(p)) return rc;
+    if (const int rc = drain(p)) return rc;            // a run still pending
     TestRows T(tp);
     const bool all = T.all;
     const int32_t n_test = T.n_test;
@@ -213,7 +212,7 @@ int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_
     const int pass_max = std::min<int>(score::kMaxPass, n_copies);
     // synchronous allocations: ordered against other host threads' graph captures
     std::lock_guard<std::mutex> lk(g_capture_mu);
-    EventPair ev;
+    EventList ev{hipEventDefault};   // [0], [1]: around the call's kernels
     DevBufs B(ctx->device);
     hipError_t e;
     if ((e = upload_test_bed(B, &d_tbed, tp, st)) != hipSuccess ||
@@ -227,7 +226,7 @@ int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_
         (!hw_s.empty() && (e = B.upload(&d_ws, hw_s, st)) != hipSuccess) ||
         (!hw_l.empty() && (e = B.upload(&d_wl, hw_l, st)) != hipSuccess) ||
         (!hf_s.empty() && (e = B.upload(&d_fs, hf_s, st)) != hipSuccess) ||
-        (!hf_l.empty() && (e = B.upload(&d_fl, hf_l, st)) != hipSuccess) || (e = ev.create()) != hipSuccess)
+        (!hf_l.empty() && (e = B.upload(&d_fl, hf_l, st)) != hipSuccess) || (e = ev.grow(2)) != hipSuccess)
         return hip_fail(ctx, "score alloc/upload: ", e);
     const uint8_t* rows = nullptr;    // the 2-bit rows the product reads and their pitch
     int64_t pitch = 0;
@@ -253,7 +252,7 @@ int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_
         rows = d_cbed;
         pitch = cpitch;
     }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev.ev0, st)) != hipSuccess)
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev[0], st)) != hipSuccess)
         return hip_fail(ctx, "score statistics: ", e);
     double *d_a = d_coef, *d_am = d_coef + ncoef, *d_k = d_coef + 2 * ncoef;
     hipLaunchKernelGGL(dbslmm_score_coef, dim3((stride + 255) / 256, n_copies), dim3(256), 0, st,
@@ -281,10 +280,10 @@ int dbslmm_plan_score(dbslmm_plan* p, const dbslmm_test_panel* tp, const dbslmm_
                            nc, n_pad, d_kc + c0, n_test, d_scores + static_cast<size_t>(c0) * n_test);
     }
     float ms = 0.0f;
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev.ev1, st)) != hipSuccess ||
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev[1], st)) != hipSuccess ||
         (e = hipMemcpyAsync(scores, d_scores, n_out * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (dropped && (e = hipMemcpyAsync(dropped, d_drop, n_copies * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) ||
-        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev.ev0, ev.ev1)) != hipSuccess)
+        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess)
         return hip_fail(ctx, "score run: ", e);
     if (gpu_ms) *gpu_ms = ms;
     return DBSLMM_OK;
@@ -463,7 +462,7 @@ static int r2_tiles_run(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
                         const std::vector<int64_t>* bp, double thr, int64_t window, uint32_t* h_masks,
                         double* h_r2, double* gpu_ms) {
     PanelImage im;
-    EventPair ev;
+    EventList ev{hipEventDefault};   // [0], [1]: around the call's kernels
     DevBufs B(ctx->device);
     int32_t *d_pos = nullptr, *d_chr = nullptr;
     int64_t* d_bp = nullptr;
@@ -481,7 +480,7 @@ static int r2_tiles_run(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
         (bp && (e = B.upload(&d_bp, *bp, ctx->stream)) != hipSuccess) ||
         (h_masks && (e = B.alloc(&d_masks, n_mask)) != hipSuccess) ||
         (h_r2 && (e = B.alloc(&d_r2, n_r2)) != hipSuccess) ||
-        (e = ev.create()) != hipSuccess || (e = hipEventRecord(ev.ev0, ctx->stream)) != hipSuccess)
+        (e = ev.grow(2)) != hipSuccess || (e = hipEventRecord(ev[0], ctx->stream)) != hipSuccess)
         return hip_fail(ctx, "r2 tiles alloc/upload: ", e);
     const int64_t kpad = im.pitch * 4;
     const dim3 grid(static_cast<unsigned>((n_tiles + 3) / 4));
@@ -495,10 +494,10 @@ static int r2_tiles_run(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, in
                            static_cast<const int64_t*>(nullptr), 0.0, int64_t(0), static_cast<uint32_t*>(nullptr),
                            d_r2);
     float ms = 0.0f;
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev.ev1, ctx->stream)) != hipSuccess ||
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev[1], ctx->stream)) != hipSuccess ||
         (h_masks && (e = hipMemcpyAsync(h_masks, d_masks, n_mask * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
         (h_r2 && (e = hipMemcpyAsync(h_r2, d_r2, n_r2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) ||
-        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev.ev0, ev.ev1)) != hipSuccess)
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess)
         return hip_fail(ctx, "r2 tiles run: ", e);
     if (gpu_ms) *gpu_ms = ms;
     return DBSLMM_OK;
@@ -605,7 +604,7 @@ int dbslmm_ld_scores(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32
     const int32_t n_tiles = static_cast<int32_t>(L.tiles.size());
     constexpr int32_t kDefaultSlice = (256 << 20) / (kL2SlotWords * static_cast<int32_t>(sizeof(double)));   // 131072 tiles
     const int32_t slice = std::min(n_tiles, a.max_tiles_per_launch > 0 ? a.max_tiles_per_launch : kDefaultSlice);
-    EventPair ev;
+    EventList ev{hipEventDefault};   // [0], [1]: around the call's kernels
     DevBufs B(ctx->device);
     int32_t *d_pos = nullptr, *d_chr = nullptr, *d_order = nullptr, *d_row_ptr = nullptr, *d_col_lo = nullptr;
     int64_t* d_bp = nullptr;
@@ -618,7 +617,7 @@ int dbslmm_ld_scores(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32
         (e = B.alloc(&d_slots, static_cast<size_t>(slice) * kL2SlotWords)) != hipSuccess ||
         (e = B.zeroed(&d_run, static_cast<size_t>(n_rows), st)) != hipSuccess ||
         (e = B.alloc(&d_out, static_cast<size_t>(n_rows))) != hipSuccess ||
-        (e = ev.create()) != hipSuccess || (e = hipEventRecord(ev.ev0, st)) != hipSuccess)
+        (e = ev.grow(2)) != hipSuccess || (e = hipEventRecord(ev[0], st)) != hipSuccess)
         return hip_fail(ctx, "ld_scores alloc/upload: ", e);
     const int64_t kpad = im.pitch * 4;
     for (int32_t t0 = 0; t0 < n_tiles; t0 += slice) {
@@ -632,9 +631,9 @@ int dbslmm_ld_scores(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, "ld_scores launch: ", e);
     }
     float ms = 0.0f;
-    if ((e = hipEventRecord(ev.ev1, st)) != hipSuccess ||
+    if ((e = hipEventRecord(ev[1], st)) != hipSuccess ||
         (e = hipMemcpyAsync(l2, d_out, static_cast<size_t>(n_rows) * sizeof(double), hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev.ev0, ev.ev1)) != hipSuccess)
+        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess)
         return hip_fail(ctx, "ld_scores run: ", e);
     if (gpu_ms) *gpu_ms = ms;
     return DBSLMM_OK;

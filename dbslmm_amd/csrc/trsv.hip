@@ -460,7 +460,7 @@ __global__ __launch_bounds__(trsv::kThreads, 1) void dbslmm_trsv_bwd(trsv::Args 
 // in their substitution order) -- so every wait is on a smaller ticket (deadlock-free) -- while
 // the blocks are interleaved by a timing model: the small blocks' many iterations stream at the
 // memory bandwidth while the largest blocks' long chains advance beside them, instead of every
-// block waiting for the largest one at the end of each pass (plan.hip, build_cheb_items).
+// block waiting for the largest one at the end of each pass (build_cheb_items, route_factor.hip).
 template <int NR>
 __global__ __launch_bounds__(trsv::kThreads, 1) void dbslmm_trsv_cheb(trsv::Args a) {
     using namespace trsv;

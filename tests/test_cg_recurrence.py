@@ -4,7 +4,7 @@ z = M_b^{-1} r, q = M_c p carried without a product with M_b.  Checks, on LD-sha
 without large SNPs: the iterate reaches the direct solve of M_c x = z; the kernel's stopping test
 (|r| <= tol lambda_min(M_c) |x|, lambda_min >= d_c + 1 - tau, or 1 - tau with large SNPs) only
 passes once the relative error is below tol; CG stops no later than the a priori Chebyshev count
-(plan.hip cheb_plan) for h2f 0.8 / 1.2 around the base 1.0."""
+(cheb_plan in route_factor.hip) for h2f 0.8 / 1.2 around the base 1.0."""
 import math
 
 import numpy as np

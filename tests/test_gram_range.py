@@ -1,5 +1,5 @@
 """The Gram at the edges of its value ranges (kernels.hip: dbslmm_bed_repitch -> dbslmm_snp_stats
--> dbslmm_gram_i8 / _big / _huge, pcg.hip's uint16 unpack, plan.hip's n_ref bounds and image cache).
+-> dbslmm_gram_i8 / _big / _huge, pcg.hip's uint16 unpack, plan_create's n_ref bounds and upload.hip's image cache).
 
 Every other Gram test draws A1 frequencies p <= 0.5 (synth.simulate), so dosage 2 is the rare
 genotype and no integer Gram entry comes near 2^15, let alone the 4 n_ref <= 65535 the uint16 Gram

@@ -343,7 +343,7 @@ def test_five_copies_under_solver_2_fall_to_the_factorisation():
     copy at sigma factors 0.6 / 0.8 / 1.0 / 1.2 / 1.4: 3.05e-10, 1.47e-12, 2.93e-15 for the base
     copy, 9.00e-12, 4.45e-10): adding a fifth h2f factor moved the results of a PCG-route problem
     from pcg_tol to cheb_tol.  run_impl now holds a run that only its copy count keeps off the PCG
-    route to pcg_tol (plan.hip: h2f_tol); measured values: DESIGN.md section 4."""
+    route to pcg_tol (run_impl: h2f_tol); measured values: DESIGN.md section 4."""
     from test_pcg_paths import FIVE, check_shard_rule, five_copies_case
     forced, sig = five_copies_case()
     auto = pcg_case(sizes=(70, 300, 200, 1030, 0, 40), n_large=(0, 0, 2, 1, 0, 0)).prob

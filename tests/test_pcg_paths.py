@@ -1,4 +1,4 @@
-"""The PCG route (pcg.hip, run_pcg in plan.hip) through everything downstream of the solve: sharded
+"""The PCG route (pcg.hip, run_pcg in route_pcg.hip) through everything downstream of the solve: sharded
 contexts, units plans, copy-split units, the variance's forced factorisation re-solve
 (pcg_pending_var), route changes on one plan and the drop-in CLI on its production route.  The
 route's own numerics are test_pcg.py's subject; here every problem has the flagship prior shift
@@ -112,7 +112,7 @@ def five_copies_case():
 
 def rule_cases():
     """(name, problem, sigmas, expected pcg_route) at the edges of the route rule (pcg_route in
-    plan.hip, problem_pcg_route in multi.hip).  d = 1 / (sigma n) is exactly 2.0 in fp64 at
+    route_pcg.hip, problem_pcg_route in multi.hip).  d = 1 / (sigma n) is exactly 2.0 in fp64 at
     n = 2^16, sigma = 2^-17 (both powers of two: the product 0.5 and its reciprocal are exact);
     the next fp64 sigma gives d = 2 - 2^-51 < 2.  The 5-copy case here factors every copy
     (h2f_mode = 1, the CLI's --h2f-merged); the default h2f mode is five_copies_case."""

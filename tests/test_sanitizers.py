@@ -6,6 +6,8 @@
   writer -- through --dry-run (stops before the first GPU call);
 * the plan's host layout (dbslmm_amd/csrc/plan_layout.hpp) through its stand-alone check
   (tests/host/layout_check.cpp, built by the same target as `layout_asan`);
+* the host-thread copies of the uploads and downloads (dbslmm_amd/csrc/host_copy.hpp) through
+  theirs (tests/host/copy_check.cpp, `copy_asan`);
 * the CPU oracle (`make -C oracle sanitize`): a standalone driver over every oracle entry point
   on the reference's test_dat panel and a synthetic panel with missing calls and n % 4 = 3.
 
@@ -96,6 +98,13 @@ def test_valid_argument_handling_under_asan_ubsan(valid_asan, args, tmp_path):
 
 def test_plan_layout_under_asan_ubsan():
     exe = _built(os.path.join(ROOT, "dbslmm_amd", "csrc"), "sanitize", os.path.join(BIN, "layout_asan"))
+    r = _run(exe, [])
+    assert _clean(r), r.stderr[-3000:]
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stderr[-3000:]
+
+
+def test_host_copy_under_asan_ubsan():
+    exe = _built(os.path.join(ROOT, "dbslmm_amd", "csrc"), "sanitize", os.path.join(BIN, "copy_asan"))
     r = _run(exe, [])
     assert _clean(r), r.stderr[-3000:]
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stderr[-3000:]

@@ -2,12 +2,12 @@
 preconditioned CG, per block, on blocks shaped like config 4's (numpy, CPU).
 
 The h2f copies of a block solve M_c x = z with M_c = M_b + delta_c P_s (P_s: the small SNPs'
-coordinates), M_b the base copy's matrix, factored once (plan.hip cheb_plan / trsv.hip).  Both
+coordinates), M_b the base copy's matrix, factored once (cheb_plan in route_factor.hip / trsv.hip).  Both
 iterations start from the base solution x_b and apply M_b^{-1} once per iteration (one forward and
 one backward substitution on the base factor); neither needs a product with M_b (the Chebyshev
 recurrence carries s = M_b d, CG carries M_b p the same way).  CG needs two dot products per
 iteration and block; the Chebyshev coefficients are a priori (interval [1, 1 + delta / (d_b + 1 -
-tau)], plan.hip:1555-1592).  Also reported: the spectrum of M_b^{-1} M_c (its extreme
+tau)], cheb_plan).  Also reported: the spectrum of M_b^{-1} M_c (its extreme
 eigenvalues) and the Chebyshev count on that measured interval.
 
     python tools/cheb_vs_cg.py [m ...]        (default 9667 2579 544; n_ref 10000)
