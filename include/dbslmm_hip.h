@@ -64,6 +64,26 @@ enum {
                                       (at tau = 1 the stopping test of a block with large SNPs,
                                       |r| <= cheb_tol (1 - tau) |x|, can never pass). */
 };
+/* A non-finite z (NaN, +Inf or -Inf in one z_s / z_l entry: a summary row whose beta is `nan` or
+ * `inf`) is data, not an error.  It makes EVERY beta of its block non-finite in every copy, as the
+ * reference's algebra does, and touches no other block: their betas, statuses and iteration counts
+ * are bit for bit those of the run without it.  The status of such a block:
+ *
+ *   route                                            status              betas        iterations
+ *   PCG (every kernel, 1 .. 4 copies)                NOT_CONVERGED (4)   non-finite   pcg_maxit
+ *   factorisation, a factored copy (base, merged,    OK (0)              non-finite   -
+ *     copy-split units, blocks of <= 63 SNPs)
+ *   factorisation, an h2f copy iterated on the base  OK (0): it ran its  non-finite   the a priori
+ *     factor (Chebyshev, CG, dbslmm_tcheb, fused)    a priori count                   count
+ *     ... CG under a pcg_maxit below that count      NOT_CONVERGED (4)   non-finite   pcg_maxit
+ *
+ * (a NaN never passes a stopping test; the factorisation has no test to fail: the matrix is sound).
+ * So a status of OK does not promise finite betas; dbslmm_plan_score drops such SNPs by its
+ * !isfinite rule, dbslmm_plan_variance reads the matrix alone and is unchanged.
+ *
+ * Every stopping rule is relative, so the solve is exactly homogeneous in z: z -> c z with c = +-2^k
+ * gives c beta bit for bit, the same statuses and the same iteration counts, as long as no z^2,
+ * (c z)^2 or squared residual leaves the normal fp64 range (tests/test_z_edges.py). */
 
 typedef struct dbslmm_ctx dbslmm_ctx;
 typedef struct dbslmm_plan dbslmm_plan;
