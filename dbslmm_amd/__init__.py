@@ -12,6 +12,8 @@ entry points mirror the reference operator interface (fboehm/DBSLMM, scr/dbslmmf
   reference panel (software/DBSLMM.R:139-145), ``ld_r2`` the dense r2 matrix of a list of rows.
 * ``ld_scores``           -- the LD scores of listed panel rows, ``ldsc_h2`` the LD score regression on
   them: the heritability the reference takes from an LDSC run (Rmd/Manual.Rmd:170).
+* ``assoc``               -- the association scan of a training panel: the per-SNP linear model with
+  a Wald test whose output (a GEMMA ``*.assoc.txt``) the reference's workflow starts from.
 * ``Plan.score``          -- the polygenic scores of a target panel for every h2f copy of the latest
   run (what the reference leaves to ``plink --score``), ``tune_r2`` the R2 index of TUNE.R on them.
 * ``Context.row_stats``   -- the exact per-row integers (sum, sum of squares, missing calls) the
@@ -30,7 +32,7 @@ from . import _lib
 from ._lib import (WORKLOAD_LEN, BLOCK_EMPTY, BLOCK_MONOMORPHIC, BLOCK_NOT_CONVERGED, BLOCK_NOT_PD,
                    BLOCK_OK, KERNEL_NAMES, SOLVER_AUTO, SOLVER_FACTOR, SOLVER_PCG, DbslmmError)
 
-__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2", "ld_r2", "clump", "ld_scores", "ldsc_h2",
+__all__ = ["Context", "Plan", "DBSLMMFIT", "BlockProblem", "bed_maf", "read_snp_std", "valid_blocks", "tune_r2", "ld_r2", "clump", "ld_scores", "ldsc_h2", "assoc", "assoc_stat_host", "student_t_two_sided",
            "DbslmmError", "BLOCK_OK", "BLOCK_EMPTY", "BLOCK_NOT_PD", "BLOCK_MONOMORPHIC",
            "BLOCK_NOT_CONVERGED", "KERNEL_NAMES", "SOLVER_AUTO", "SOLVER_FACTOR", "SOLVER_PCG"]
 
@@ -493,6 +495,96 @@ def ldsc_h2(chi2, n, l2, m, intercept=None, n_blocks: int = 200, chisq_max: floa
         raise DbslmmError(f"ldsc_fit failed (rc={rc}): bad arguments")
     return dict(h2=res.h2, h2_se=res.h2_se, intercept=res.intercept, intercept_se=res.intercept_se,
                 mean_chi2=res.mean_chi2, n=int(res.n_used), status=int(res.status))
+
+
+def assoc(ctx: Context, bed: np.ndarray, n_total: int, pheno, covar=None, keep=None, rows=None,
+          chunk_indiv: int = 0, products: bool = False) -> dict:
+    """The association scan (dbslmm_assoc): per bed row a linear model of every phenotype on the row's
+    mean-imputed dosage, the intercept and the covariates, with a Wald test.  pheno: n_total or
+    n_total x P; covar: n_total x (c - 1) or None; keep: n_total flags or None.  The sample is the kept
+    individuals with finite phenotypes and covariates.  rows: bed rows in any order (None: all).
+    Returns a dict: n_mis, n_obs, status [rows]; af [rows]; beta, se, tstat, p [P, rows] (NaN unless
+    status is 0); with products also prod_d, prod_m [rows, c - 1 + P], the raw products.  chunk_indiv:
+    individuals per chunk of the fixed-order sum (a multiple of 64; 0 = the library's constant).  The
+    event time of the kernels is kept in ctx.assoc_gpu_ms."""
+    bed = np.ascontiguousarray(bed, dtype=np.uint8)
+    y = np.ascontiguousarray(pheno, dtype=np.float64)
+    if y.ndim == 1:
+        y = np.ascontiguousarray(y[:, None])
+    if y.ndim != 2 or y.shape[0] != n_total:
+        raise ValueError("pheno: n_total or n_total x P")
+    w = None
+    if covar is not None:
+        w = np.ascontiguousarray(covar, dtype=np.float64)
+        if w.ndim == 1:
+            w = np.ascontiguousarray(w[:, None])
+        if w.ndim != 2 or w.shape[0] != n_total:
+            raise ValueError("covar: n_total x (c - 1)")
+        if w.shape[1] == 0:
+            w = None
+    k = None
+    if keep is not None:
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if k.shape != (n_total,):
+            raise ValueError("keep: n_total flags")
+    if rows is None:
+        n_rows = (bed.size - 3) // ((n_total + 3) // 4)
+        r = None
+    else:
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("rows: a list of bed rows")
+        n_rows = len(r)
+    P, c1 = y.shape[1], 0 if w is None else w.shape[1]
+    m = max(1, n_rows)
+    n_mis, n_obs, status = (np.zeros(m, dtype=np.int32) for _ in range(3))
+    af = np.zeros(m)
+    beta, se, tstat, p = (np.zeros((P, m)) for _ in range(4))
+    pd = np.zeros((m, c1 + P)) if products else None
+    pm = np.zeros((m, c1 + P)) if products else None
+    ms = np.zeros(1)
+    args = _lib.AssocArgs(_ptr(k), _ptr(y), _ptr(w), P, c1, int(chunk_indiv))
+    ctx.check(ctx.lib.dbslmm_assoc(ctx.h, _ptr(bed), bed.size, n_total, n_rows, _ptr(r), C.byref(args), _ptr(n_mis),
+                                   _ptr(n_obs), _ptr(af), _ptr(beta), _ptr(se), _ptr(tstat), _ptr(p), _ptr(status),
+                                   _ptr(pd), _ptr(pm), _ptr(ms)), "assoc")
+    ctx.assoc_gpu_ms = float(ms[0])
+    out = dict(n_mis=n_mis[:n_rows], n_obs=n_obs[:n_rows], status=status[:n_rows], af=af[:n_rows],
+               beta=beta[:, :n_rows], se=se[:, :n_rows], tstat=tstat[:, :n_rows], p=p[:, :n_rows])
+    if products:
+        out.update(prod_d=pd[:n_rows], prod_m=pm[:n_rows])
+    return out
+
+
+def assoc_stat_host(n: int, c: int, n1, n2, nm, t, yy) -> dict:
+    """The finish of the scan on the host (dbslmm_assoc_stat_host; no GPU): rows with the counts n1, n2,
+    nm over n individuals and the products t [rows, c - 1 + P] of their mean-imputed dosages with
+    [Q_1 .. | Yr]; yy [P] = |Yr_p|^2; c counts the intercept.  Returns the dict of `assoc` without n_mis."""
+    n1, n2, nm = (np.ascontiguousarray(a, dtype=np.int32) for a in (n1, n2, nm))
+    yy = np.ascontiguousarray(np.atleast_1d(yy), dtype=np.float64)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    n_rows, P, c1 = len(n1), len(yy), int(c) - 1
+    if not (n1.shape == n2.shape == nm.shape and n1.ndim == 1 and t.shape == (n_rows, c1 + P)):
+        raise ValueError("n1, n2, nm: one entry per row; t: rows x (c - 1 + P)")
+    m = max(1, n_rows)
+    n_obs, status = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+    af = np.zeros(m)
+    beta, se, tstat, p = (np.zeros((P, m)) for _ in range(4))
+    rc = _lib.load().dbslmm_assoc_stat_host(int(n), c1, P, n_rows, _ptr(n1), _ptr(n2), _ptr(nm), _ptr(t), _ptr(yy),
+                                            _ptr(n_obs), _ptr(af), _ptr(beta), _ptr(se), _ptr(tstat), _ptr(p),
+                                            _ptr(status))
+    if rc != 0:
+        raise DbslmmError(f"assoc_stat_host failed (rc={rc}): bad arguments")
+    return dict(n_obs=n_obs[:n_rows], status=status[:n_rows], af=af[:n_rows], beta=beta[:, :n_rows],
+                se=se[:, :n_rows], tstat=tstat[:, :n_rows], p=p[:, :n_rows])
+
+
+def student_t_two_sided(t: float, df: float) -> float:
+    """2 P(t_df <= -|t|) (dbslmm_student_t_two_sided; host only): NaN for a non-finite argument."""
+    out = C.c_double()
+    rc = _lib.load().dbslmm_student_t_two_sided(float(t), float(df), C.byref(out))
+    if rc != 0:
+        raise DbslmmError(f"student_t_two_sided failed (rc={rc})")
+    return float(out.value)
 
 
 def tune_r2(scores, pheno) -> tuple[np.ndarray, int]:

@@ -23,9 +23,10 @@ EXPORTS = (
     "dbslmm_shard_plan", "dbslmm_plan_create_units", "dbslmm_shard_plan_problem",
     "dbslmm_plan_block_iters", "dbslmm_bed_row_stats", "dbslmm_out_ranges", "dbslmm_plan_score",
     "dbslmm_ld_r2", "dbslmm_clump", "dbslmm_ld_scores", "dbslmm_ldsc_fit",
+    "dbslmm_assoc", "dbslmm_assoc_stat_host", "dbslmm_student_t_two_sided",
 )
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 K_UNPACK, K_GRAM, K_CHOL_LARGE, K_CHOL_SMALL, K_CHOL_TILED, K_TRSV, K_PCG, K_PCG_BLOCK = 0, 1, 2, 3, 4, 5, 6, 7
 KERNEL_NAMES = ("dbslmm_unpack_stats", "dbslmm_gram", "dbslmm_chol_large", "dbslmm_chol_small",
                 "dbslmm_tchol", "dbslmm_trsv", "dbslmm_pcg", "dbslmm_pcg_block")
@@ -96,6 +97,16 @@ class LdscResult(C.Structure):
 
 LDSC_OK, LDSC_TOO_FEW, LDSC_SINGULAR = 0, 1, 2
 
+
+class AssocArgs(C.Structure):
+    """dbslmm_assoc_args: keep flags, phenotypes [n_total x n_pheno], covariates [n_total x n_covar] (or
+    null), individuals per chunk (0 = the library's constant)."""
+    _fields_ = [("keep", C.c_void_p), ("pheno", C.c_void_p), ("covar", C.c_void_p), ("n_pheno", C.c_int32),
+                ("n_covar", C.c_int32), ("chunk_indiv", C.c_int32)]
+
+
+ASSOC_OK, ASSOC_NO_CALL, ASSOC_MONOMORPHIC, ASSOC_COLLINEAR = 0, 1, 2, 3
+
 _lib = None
 
 
@@ -142,6 +153,9 @@ def load(path: str | None = None):
     L.dbslmm_clump.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, P(ClumpArgs), V, V, V]
     L.dbslmm_ld_scores.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, P(L2Args), V, V, V]
     L.dbslmm_ldsc_fit.argtypes = [C.c_int64, V, V, V, C.c_double, P(LdscArgs), P(LdscResult)]
+    L.dbslmm_assoc.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, P(AssocArgs)] + [V] * 11
+    L.dbslmm_assoc_stat_host.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [V] * 12
+    L.dbslmm_student_t_two_sided.argtypes = [C.c_double, C.c_double, P(C.c_double)]
     L.dbslmm_valid_blocks.argtypes = [V, V, C.c_int64, C.c_int32, C.c_int32, V, V, V, V, V, V]
     L.dbslmm_plan_variance.argtypes = [V, P(TestPanel), V, V]
     L.dbslmm_plan_score.argtypes = [V, P(TestPanel), P(ScoreArgs), C.c_int32, V, V, V, V]

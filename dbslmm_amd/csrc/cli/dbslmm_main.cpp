@@ -78,6 +78,10 @@ struct Param {                     // PARAM, scr/dbslmm.hpp:29-45 (initialised h
     bool ldsc = false;              // --ldsc: LD scores and LD score regression (ldsc_mode.hpp)
     string out, intercept = "free"; // --out PREFIX, --intercept free|X
     double ld_wind_kb = 1000.0, chisq_max = 0.0;   // --ld-wind-kb, --chisq-max (0 = off)
+    bool assoc = false;             // --assoc: the association scan of training panels (assoc_mode.hpp)
+    string pheno, pheno_col, covar, keep;   // --pheno FILE, --pheno-col K[,K2,..], --covar FILE, --keep FILE
+    double maf_min = 0.0, miss_max = 1.0;   // --maf-min, --miss-max
+    bool assoc_header = false;      // --assoc-header
 };
 
 // The host rows keep string_views into the mmap'd input files (no per-SNP allocation).
@@ -169,7 +173,19 @@ void print_help() {
               << " --out     [prefix]     --ldsc: prefix of the output files\n"
               << " --ld-wind-kb [num]     --ldsc: LD score window in kb, default 1000\n"
               << " --intercept [free|num] --ldsc: free intercept (default) or fixed at num\n"
-              << " --chisq-max [num]      --ldsc: drop SNPs with chi2 above num (default: no filter)\n";
+              << " --chisq-max [num]      --ldsc: drop SNPs with chi2 above num (default: no filter)\n"
+              << " --assoc                another mode: the association scan of the -r training panels (comma\n"
+              << "                        list, one after the other): per SNP a linear model with a Wald test,\n"
+              << "                        written as GEMMA's 11 columns to <out>.assoc.txt (<out>.<k>.assoc.txt\n"
+              << "                        with several phenotypes), the rows left out to <out>.assoc.skipped:\n"
+              << "                        the input of --ldsc and of --summary / --pth\n"
+              << " --pheno   [filename]   --assoc: `FID IID v1 v2 ..` lines; default: column 6 of the .fam\n"
+              << " --pheno-col [list]     --assoc: value columns of --pheno from 1, e.g. 1,3 (default 1)\n"
+              << " --covar   [filename]   --assoc: `FID IID c1 c2 ..` lines (the intercept is added)\n"
+              << " --keep    [filename]   --assoc: indicator file, one line per individual, non-zero = kept\n"
+              << " --maf-min [num]        --assoc: leave out rows with a folded allele frequency below num\n"
+              << " --miss-max [num]       --assoc: leave out rows with a missing fraction above num\n"
+              << " --assoc-header         --assoc: write the column names as a first line\n";
 }
 
 // DBSLMM::Assign (scr/dbslmm.cpp:67-172): a flag's value is skipped when it starts with '-'.
@@ -223,6 +239,14 @@ void assign(int argc, char** argv, Param& p) {
         else if (!strcmp(a, "--ld-wind-kb")) { if ((v = take_num(i))) p.ld_wind_kb = atof(v); }
         else if (!strcmp(a, "--intercept")) { if ((v = take_num(i))) p.intercept = v; }
         else if (!strcmp(a, "--chisq-max")) { if ((v = take_num(i))) p.chisq_max = atof(v); }
+        else if (!strcmp(a, "--assoc")) p.assoc = true;
+        else if (!strcmp(a, "--pheno")) { if ((v = take(i))) p.pheno = v; }
+        else if (!strcmp(a, "--pheno-col")) { if ((v = take_num(i))) p.pheno_col = v; }
+        else if (!strcmp(a, "--covar")) { if ((v = take(i))) p.covar = v; }
+        else if (!strcmp(a, "--keep")) { if ((v = take(i))) p.keep = v; }
+        else if (!strcmp(a, "--maf-min")) { if ((v = take_num(i))) p.maf_min = atof(v); }
+        else if (!strcmp(a, "--miss-max")) { if ((v = take_num(i))) p.miss_max = atof(v); }
+        else if (!strcmp(a, "--assoc-header")) p.assoc_header = true;
         else if (!strcmp(a, "--dry-run")) p.dry_run = true;
         else if (!strcmp(a, "--timing")) p.timing = true;
         else if (!strcmp(a, "--repeat")) { if ((v = take(i))) p.repeat = std::max(0, atoi(v)); }
@@ -594,6 +618,7 @@ int64_t count_lines(string_view t) {
 }
 
 #include "ldsc_mode.hpp"
+#include "assoc_mode.hpp"
 
 // One <eff>.txt per h2f factor (scr/dbslmm.cpp:353-364, 391-395): large rows first, then small
 // rows, "snp a1 beta beta_noscl flag"; ostream's default double format = printf %g at precision 6
@@ -702,6 +727,7 @@ int main(int argc, char** argv) {
     Param p;
     assign(argc, argv, p);
     if (p.ldsc) return ldsc_mode(p);
+    if (p.assoc) return assoc_mode(p);
 
     std::cout << "Options: \n-s:      " << p.s << "\n-l:      " << p.l << "\n-r:      " << p.r
               << "\n-nsnp:   " << p.nsnp << "\n-n:      " << p.n << "\n-mafMax: " << p.mafMax

@@ -1,7 +1,8 @@
 // panel_api.hip -- the entry points that read a panel beside the solve (included by plan.hip, inside
 // its extern "C" block: same translation unit): the test-set variance and polygenic scores of a
 // plan, and the context-level tools on a .bed (MAF, row statistics, standardised rows, the `valid`
-// terms, LD r2, clumping and LD scores; the host-only LD score regression).  Each allocates for one call on a local DevBufs (dev_bufs.hpp).
+// terms, LD r2, clumping, LD scores and the association scan; the host-only LD score regression,
+// scan finish and t tail).  Each allocates for one call on a local DevBufs (dev_bufs.hpp).
 
 // "<what>: <HIP error>" as the context's error
 static int hip_fail(dbslmm_ctx* ctx, const char* what, hipError_t e) {
@@ -649,5 +650,113 @@ int dbslmm_ldsc_fit(int64_t n, const double* chi2, const double* n_obs, const do
     const ldsc::Result r = ldsc::fit(n, chi2, n_obs, l2, m, a.fixed_intercept != 0, a.intercept,
                                      a.n_blocks > 0 ? a.n_blocks : 200, a.chisq_max);
     *out = dbslmm_ldsc_result{r.h2, r.h2_se, r.intercept, r.intercept_se, r.mean_chi2, r.n_used, r.status};
+    return DBSLMM_OK;
+}
+
+// Association scan (assoc.hip): the design on the host (assoc_layout.hpp), then the counts, one
+// product launch per group of 16 columns of V, and the finish.
+int dbslmm_assoc(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_total, int32_t n_rows,
+                 const int32_t* rows, const dbslmm_assoc_args* args, int32_t* n_mis, int32_t* n_obs, double* af,
+                 double* beta, double* se, double* tstat, double* p, int32_t* status, double* prod_d,
+                 double* prod_m, double* gpu_ms) {
+    if (!ctx) return DBSLMM_E_ARG;
+    ON_FIRST_DEVICE(ctx, dbslmm_assoc(ctx0_, bed, bed_len, n_total, n_rows, rows, args, n_mis, n_obs, af, beta, se,
+                                      tstat, p, status, prod_d, prod_m, gpu_ms));
+    if (const int rc = ctx_ready(ctx)) return rc;
+    ARG_CHECK(ctx, bed && args && n_total >= 1 && n_rows >= 0, "bad arguments");
+    ARG_CHECK(ctx, n_rows == 0 || (n_mis && n_obs && af && beta && se && tstat && p && status), "null outputs");
+    ARG_CHECK(ctx, (prod_d == nullptr) == (prod_m == nullptr), "prod_d and prod_m: both or neither");
+    ARG_CHECK(ctx, args->chunk_indiv >= 0 && args->chunk_indiv % kAssocStage == 0,
+              "chunk_indiv must be a multiple of 64 (0: the default)");
+    if (rows) {
+        if (const int rc = rows_in_bed(ctx, bed_len, n_total, rows, n_rows)) return rc;
+    } else {
+        ARG_CHECK(ctx, bed_len >= 3 + n_rows * bed_row_bytes(n_total), "bed image shorter than n_rows rows");
+    }
+    const int64_t n_pad = round_up(n_total, gram::kKpadAlign);     // the individuals of an image row
+    assoc::Design D;
+    if (!assoc::build_design(n_total, n_pad, args->keep, args->pheno, args->n_pheno, args->covar, args->n_covar, D)) {
+        ctx->err = "assoc: " + D.err;
+        return DBSLMM_E_ARG;
+    }
+    if (gpu_ms) *gpu_ms = 0.0;
+    if (n_rows == 0) return DBSLMM_OK;
+    const int32_t n_stages = static_cast<int32_t>(n_pad / kAssocStage);
+    const int32_t spc = (args->chunk_indiv > 0 ? args->chunk_indiv : kAssocChunkIndiv) / kAssocStage;
+    const int32_t n_chunks = (n_stages + spc - 1) / spc;
+    ARG_CHECK(ctx, n_chunks <= 65535, "chunk_indiv too small for this panel (more than 65535 chunks)");
+    const int32_t n_tiles = (n_rows + kAssocRows - 1) / kAssocRows;
+    KEY_CHECK(ctx, bed, bed_len, n_total);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    PanelImage im;
+    hipError_t e;
+    if ((e = panel_image(ctx, bed, bed_len, n_total, &im)) != hipSuccess) return hip_fail(ctx, "assoc panel image: ", e);
+    // the image row of every tile row: the zero-dosage row past the list
+    std::vector<int32_t> rows16(static_cast<size_t>(n_tiles) * kAssocRows, im.n_rows);
+    for (int32_t j = 0; j < n_rows; ++j) rows16[static_cast<size_t>(j)] = rows ? rows[j] : j;
+    const int32_t P = D.P, c1 = D.c1, n_cols = D.n_cols;
+    const size_t n_part = static_cast<size_t>(D.n_groups) * n_chunks * n_tiles * assoc::kTileWords;
+    const size_t n_prod = static_cast<size_t>(n_rows) * n_cols, n_stat = static_cast<size_t>(n_rows) * P;
+    EventList ev{hipEventDefault};   // [0], [1]: around the call's kernels
+    DevBufs B(ctx->device);
+    int32_t *d_rows = nullptr, *d_int = nullptr;   // d_int: n_mis | n_obs | status
+    uint32_t* d_mask = nullptr;
+    v4i* d_counts = nullptr;
+    double *d_V = nullptr, *d_yy = nullptr, *d_part = nullptr, *d_prod = nullptr, *d_out = nullptr;   // d_out: af | beta | se | T | p
+    if ((e = B.upload(&d_rows, rows16, st)) != hipSuccess || (e = B.upload(&d_mask, D.mask, st)) != hipSuccess ||
+        (e = B.upload(&d_V, D.V, st)) != hipSuccess || (e = B.upload(&d_yy, D.yy, st)) != hipSuccess ||
+        (e = B.alloc(&d_counts, static_cast<size_t>(n_rows))) != hipSuccess ||
+        (e = B.alloc(&d_part, 2 * n_part)) != hipSuccess || (e = B.alloc(&d_prod, 2 * n_prod)) != hipSuccess ||
+        (e = B.alloc(&d_int, 3 * static_cast<size_t>(n_rows))) != hipSuccess ||
+        (e = B.alloc(&d_out, static_cast<size_t>(n_rows) + 4 * n_stat)) != hipSuccess ||
+        (e = ev.grow(2)) != hipSuccess || (e = hipEventRecord(ev[0], st)) != hipSuccess)
+        return hip_fail(ctx, "assoc alloc/upload: ", e);
+    hipLaunchKernelGGL(dbslmm_assoc_counts, dim3(static_cast<unsigned>((n_rows + 3) / 4)), dim3(256), 0, st,
+                       im.mem.get(), im.pitch, d_rows, n_rows, d_mask, d_counts);
+    const size_t group_part = n_part / D.n_groups;
+    for (int32_t g = 0; g < D.n_groups; ++g)
+        hipLaunchKernelGGL(dbslmm_assoc_tiles, dim3(static_cast<unsigned>((n_tiles + assoc::kTileWaves - 1) / assoc::kTileWaves), n_chunks),
+                           dim3(256), 0, st, im.mem.get(), im.pitch, d_rows, n_tiles,
+                           d_V + static_cast<size_t>(g) * n_pad * kAssocCols, n_stages, spc, d_part + g * group_part,
+                           d_part + n_part + g * group_part);
+    double* d_af = d_out;
+    double *d_beta = d_af + n_rows, *d_se = d_beta + n_stat, *d_t = d_se + n_stat, *d_p = d_t + n_stat;
+    hipLaunchKernelGGL(dbslmm_assoc_finish, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, st, d_part,
+                       d_part + n_part, D.n_groups, n_chunks, n_tiles, n_rows, c1, P, D.n, d_counts, d_yy, d_prod,
+                       d_prod + n_prod, d_int, d_int + n_rows, d_af, d_beta, d_se, d_t, d_p, d_int + 2 * static_cast<size_t>(n_rows));
+    float ms = 0.0f;
+    const size_t ni = static_cast<size_t>(n_rows) * sizeof(int32_t), nd = static_cast<size_t>(n_rows) * sizeof(double);
+    auto down = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); };
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipEventRecord(ev[1], st)) != hipSuccess ||
+        (e = down(n_mis, d_int, ni)) != hipSuccess || (e = down(n_obs, d_int + n_rows, ni)) != hipSuccess ||
+        (e = down(status, d_int + 2 * static_cast<size_t>(n_rows), ni)) != hipSuccess || (e = down(af, d_af, nd)) != hipSuccess ||
+        (e = down(beta, d_beta, nd * P)) != hipSuccess || (e = down(se, d_se, nd * P)) != hipSuccess ||
+        (e = down(tstat, d_t, nd * P)) != hipSuccess || (e = down(p, d_p, nd * P)) != hipSuccess ||
+        (prod_d && ((e = down(prod_d, d_prod, n_prod * sizeof(double))) != hipSuccess ||
+                    (e = down(prod_m, d_prod + n_prod, n_prod * sizeof(double))) != hipSuccess)) ||
+        (e = hipStreamSynchronize(st)) != hipSuccess || (e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess)
+        return hip_fail(ctx, "assoc run: ", e);
+    if (gpu_ms) *gpu_ms = ms;
+    return DBSLMM_OK;
+}
+
+// The finish of the scan on caller-supplied counts and products (assoc_fit.hpp): host only.
+int dbslmm_assoc_stat_host(int64_t n, int32_t n_covar, int32_t n_pheno, int32_t n_rows, const int32_t* n1,
+                           const int32_t* n2, const int32_t* nm, const double* t, const double* yy,
+                           int32_t* n_obs, double* af, double* beta, double* se, double* tstat, double* p,
+                           int32_t* status) {
+    if (n_pheno < 1 || n_covar < 0 || n_rows < 0 || n - n_covar - 2 < 1 || !yy) return DBSLMM_E_ARG;
+    if (n_rows > 0 && !(n1 && n2 && nm && t && n_obs && af && beta && se && tstat && p && status)) return DBSLMM_E_ARG;
+    const int64_t n_cols = static_cast<int64_t>(n_covar) + n_pheno;
+    for (int32_t j = 0; j < n_rows; ++j)
+        status[j] = assoc::finish_row(n, n_covar, n_pheno, n1[j], n2[j], nm[j], t + j * n_cols, nullptr, yy, n_obs + j,
+                                      af + j, beta + j, se + j, tstat + j, p + j, n_rows);
+    return DBSLMM_OK;
+}
+
+int dbslmm_student_t_two_sided(double t, double df, double* p_out) {
+    if (!p_out) return DBSLMM_E_ARG;
+    *p_out = assoc::student_t_two_sided(t, df);
     return DBSLMM_OK;
 }

@@ -54,6 +54,7 @@
 #include "pcg.hip"
 #include "clump.hip"
 #include "ldscore.hip"
+#include "assoc.hip"
 
 #include "plan_state.hpp"
 

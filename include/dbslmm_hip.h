@@ -16,6 +16,8 @@
  *                         the reference panel): the index SNPs of a candidate list.
  *   dbslmm_ld_scores,     the heritability the reference takes from an LDSC run (Rmd/Manual.Rmd:170):
  *   dbslmm_ldsc_fit       LD scores of the reference panel and the LD score regression.
+ *   dbslmm_assoc          the association scan that makes the summary statistics the reference reads
+ *                         (a GEMMA *.assoc.txt, Rmd/Manual.Rmd): per-SNP linear model, Wald test.
  *   dbslmm_read_snp_std   IO::readSNPIm + SNPPROC::nomalizeVec (dtpr.cpp:285-364, 375-380) for a
  *                         list of bed rows: standardised fp64 columns (parity / diagnostics).
  *
@@ -35,7 +37,7 @@
 extern "C" {
 #endif
 
-#define DBSLMM_ABI_VERSION 21
+#define DBSLMM_ABI_VERSION 22
 
 enum {
     DBSLMM_OK = 0,
@@ -585,6 +587,54 @@ typedef struct dbslmm_ldsc_result {
 } dbslmm_ldsc_result;
 int dbslmm_ldsc_fit(int64_t n, const double* chi2, const double* n_obs, const double* l2, double m,
                     const dbslmm_ldsc_args* args, dbslmm_ldsc_result* out);
+
+/* Association scan (ABI 22; assoc.hip, assoc_fit.hpp states the model in full): the summary
+ * statistics of a training panel -- per SNP row a linear model of each phenotype on the row's
+ * mean-imputed dosage, the intercept and the covariates, with a Wald test: the 11-column GEMMA
+ * *.assoc.txt the reference's workflow starts from.
+ *   keep    n_total flags (null: all); an individual is in the sample S when its flag is non-zero and
+ *           all of its phenotypes and covariates are finite.  n = |S|, c = n_covar + 1 (the intercept
+ *           is added by the library), df = n - c - 1 >= 1.
+ *   pheno   n_total x n_pheno, covar n_total x n_covar (null when n_covar = 0), row-major fp64.
+ *   chunk_indiv   individuals per chunk of the fixed-order reduction: a multiple of 64; 0 = the
+ *           library's constant (4096).  The same call with the same chunk_indiv gives the same bits on
+ *           every run; a row's result does not depend on the other rows of the call.
+ * rows (null: 0 .. n_rows - 1) lists bed rows in any order, repeats allowed.  Outputs: n_mis, n_obs,
+ * status [n_rows] int32; af [n_rows]; beta, se, tstat, p [n_pheno x n_rows] fp64.  For a status other
+ * than DBSLMM_ASSOC_OK beta, se, tstat and p are NaN (af too without an observed call); the integers are
+ * always reported.  prod_d / prod_m (optional, both or neither) [n_rows x (n_covar + n_pheno)]: the raw
+ * products of the row's observed dosages / missing-call mask with the columns [Q_1 .. | Yr] of the
+ * residualised design (tests, diagnostics).  gpu_ms (optional) = event time of the kernels.
+ * DBSLMM_E_ARG for n_pheno < 1, df < 1, a rank-deficient covariate matrix, a chunk_indiv that is
+ * negative or no multiple of 64, or a row outside the panel.  Mixed models, logistic models and
+ * per-trait sample masks are out of scope.  Panel-key rules of dbslmm_bed_maf; a multi-device context
+ * runs the scan on its first device. */
+enum { DBSLMM_ASSOC_OK = 0, DBSLMM_ASSOC_NO_CALL = 1, DBSLMM_ASSOC_MONOMORPHIC = 2, DBSLMM_ASSOC_COLLINEAR = 3 };
+typedef struct dbslmm_assoc_args {
+    const uint8_t* keep;
+    const double* pheno;
+    const double* covar;
+    int32_t n_pheno;
+    int32_t n_covar;
+    int32_t chunk_indiv;
+} dbslmm_assoc_args;
+int dbslmm_assoc(dbslmm_ctx* ctx, const uint8_t* bed, int64_t bed_len, int32_t n_total, int32_t n_rows,
+                 const int32_t* rows, const dbslmm_assoc_args* args, int32_t* n_mis, int32_t* n_obs, double* af,
+                 double* beta, double* se, double* tstat, double* p, int32_t* status, double* prod_d,
+                 double* prod_m, double* gpu_ms);
+
+/* The finish of dbslmm_assoc on the host (no context, no GPU): row j has the counts n1[j], n2[j],
+ * nm[j] over n individuals and the products t[j x (n_covar + n_pheno) ..] of its mean-imputed dosages
+ * with [Q_1 .. | Yr]; yy [n_pheno] = |Yr_p|^2.  Outputs as dbslmm_assoc's.  DBSLMM_E_ARG for null
+ * arrays, n_pheno < 1, n_covar < 0 or n - n_covar - 2 < 1. */
+int dbslmm_assoc_stat_host(int64_t n, int32_t n_covar, int32_t n_pheno, int32_t n_rows, const int32_t* n1,
+                           const int32_t* n2, const int32_t* nm, const double* t, const double* yy,
+                           int32_t* n_obs, double* af, double* beta, double* se, double* tstat, double* p,
+                           int32_t* status);
+
+/* 2 P(t_df <= -|t|) through the regularised incomplete beta function (host only).  *p_out = NaN for a
+ * non-finite t or df or df <= 0; DBSLMM_E_ARG for a null p_out. */
+int dbslmm_student_t_two_sided(double t, double df, double* p_out);
 
 /* readSNPIm + nomalizeVec for rows pos[0..n_rows): out is n_ref x n_rows column-major fp64
  * (column j = standardised dosages of bed row pos[j]); maf (optional) n_rows entries. */

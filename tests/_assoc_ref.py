@@ -1,0 +1,151 @@
+"""NumPy restatement of the association scan's model ("Association scan"; the C++ is
+dbslmm_amd/csrc/assoc_layout.hpp + assoc_fit.hpp + assoc.hip), parameterised by dtype (float64 or
+longdouble) and by the order of the sums over individuals.  Test infrastructure only."""
+from __future__ import annotations
+
+import numpy as np
+import scipy.stats
+
+OK, NO_CALL, MONOMORPHIC, COLLINEAR = 0, 1, 2, 3
+COLLINEAR_TOL = 1e-12
+
+
+def decode(bed, n_total, rows=None):
+    """(g, miss) of the listed .bed rows: g the dosage (readSNPIm: 00 -> 2, 10 -> 1, 11 -> 0; 0 where
+    missing), miss the 01 calls; both [rows, n_total]."""
+    bps = (n_total + 3) // 4
+    body = np.asarray(bed, dtype=np.uint8)[3:]
+    body = body[:body.size // bps * bps].reshape(-1, bps)
+    if rows is not None:
+        body = body[np.asarray(rows, dtype=np.int64)]
+    codes = ((body[:, :, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(body.shape[0], -1)[:, :n_total]
+    g = np.select([codes == 0, codes == 2], [2, 1], 0).astype(np.int8)
+    return g, codes == 1
+
+
+def encode(g, miss=None):
+    """The .bed image (magic included) of dosages g [rows, n_total] (missing where miss); the unused
+    bits of a row's last byte are zero, as PLINK writes them."""
+    g = np.asarray(g)
+    code = np.select([g == 2, g == 1], [0, 2], 3).astype(np.uint8)
+    if miss is not None:
+        code[np.asarray(miss, dtype=bool)] = 1
+    n_rows, n_total = code.shape
+    pad = (-n_total) % 4
+    code = np.concatenate([code, np.zeros((n_rows, pad), dtype=np.uint8)], axis=1).reshape(n_rows, -1, 4)
+    body = (code[:, :, 0] | (code[:, :, 1] << 2) | (code[:, :, 2] << 4) | (code[:, :, 3] << 6)).astype(np.uint8)
+    return np.concatenate([np.array([0x6C, 0x1B, 0x01], dtype=np.uint8), body.reshape(-1)])
+
+
+def fsum(terms, grouped=False):
+    """The sum of terms over axis 0 (the individuals) in a fixed order: one sequential chain, or
+    (grouped) 4-wide groups ((a0 + a1) + a2) + a3 added in order inside chunks of 64 individuals, the
+    chunks added in order."""
+    t = np.asarray(terms)
+    if not grouped:
+        return np.cumsum(t, axis=0)[-1] if t.shape[0] else np.zeros(t.shape[1:], dtype=t.dtype)
+    pad = (-t.shape[0]) % 64
+    t = np.concatenate([t, np.zeros((pad,) + t.shape[1:], dtype=t.dtype)], axis=0)
+    t = t.reshape((-1, 16, 4) + t.shape[1:])
+    g4 = ((t[:, :, 0] + t[:, :, 1]) + t[:, :, 2]) + t[:, :, 3]
+    return np.cumsum(np.cumsum(g4, axis=1)[:, -1], axis=0)[-1]
+
+
+def design(n_total, pheno, covar=None, keep=None, dtype=np.float64):
+    """S, the Householder QR of W = [1 | covar] over S, Yr and yy, V = [Q_1 .. | Yr] scattered to all
+    n_total individuals (zero rows outside S)."""
+    y = np.asarray(pheno, dtype=np.float64).reshape(n_total, -1)
+    w = np.zeros((n_total, 0)) if covar is None else np.asarray(covar, dtype=np.float64).reshape(n_total, -1)
+    ok = np.ones(n_total, dtype=bool) if keep is None else np.asarray(keep) != 0
+    ok = ok & np.all(np.isfinite(y), axis=1) & np.all(np.isfinite(w), axis=1)
+    sel = np.flatnonzero(ok)
+    n, c, P = len(sel), w.shape[1] + 1, y.shape[1]
+    if P < 1 or n - c - 1 < 1:
+        raise ValueError("P >= 1 and n - c - 1 >= 1 are needed")
+    W = np.concatenate([np.ones((n, 1)), w[sel]], axis=1).astype(dtype)
+    A = W.copy()
+    vs = []
+    for k in range(c):
+        nrm = np.sqrt(np.sum(A[k:, k] * A[k:, k]))
+        if not nrm > 1e-10 * np.sqrt(np.sum(W[:, k] * W[:, k])):
+            raise ValueError("rank-deficient covariates")
+        alpha = -nrm if A[k, k] > 0 else nrm
+        v = A[k:, k].copy()
+        v[0] -= alpha
+        beta = 2 / np.sum(v * v)
+        A[k:, k + 1:] -= np.outer(v, beta * (v @ A[k:, k + 1:]))
+        A[k:, k] = 0
+        A[k, k] = alpha
+        vs.append((v, beta))
+    Q = np.zeros((n, c), dtype=dtype)
+    Q[:c, :c] = np.eye(c, dtype=dtype)
+    for k in range(c - 1, -1, -1):
+        v, beta = vs[k]
+        Q[k:] -= np.outer(v, beta * (v @ Q[k:]))
+    Y = y[sel].astype(dtype)
+    Yr = Y - Q @ (Q.T @ Y)
+    yy = np.sum(Yr * Yr, axis=0)
+    V = np.zeros((n_total, c - 1 + P), dtype=dtype)
+    V[sel] = np.concatenate([Q[:, 1:], Yr], axis=1)
+    return dict(sel=sel, n=n, c=c, P=P, Q=Q, V=V, yy=yy, in_s=ok)
+
+
+def finish(n, c, n1, n2, nm, t, yy, dtype=np.float64):
+    """The per-row finish from the counts and the products t [rows, c - 1 + P]."""
+    n1, n2, nm = (np.asarray(a, dtype=np.int64) for a in (n1, n2, nm))
+    t = np.asarray(t, dtype=dtype)
+    yy = np.asarray(yy, dtype=dtype)
+    P = len(yy)
+    n_obs = n - nm
+    s1, s2 = n1 + 2 * n2, n1 + 4 * n2
+    status = np.zeros(len(n1), dtype=np.int32)
+    status[s2 * n_obs == s1 * s1] = MONOMORPHIC
+    status[n_obs <= 0] = NO_CALL
+    with np.errstate(all="ignore"):
+        mu = s1.astype(dtype) / n_obs.astype(dtype)
+        mu2 = mu * mu
+        ssx = (s2.astype(dtype) + mu2 * nm.astype(dtype)) - mu2 * dtype(n)
+        xPx = ssx.copy()
+        for k in range(c - 1):
+            xPx = xPx - t[:, k] * t[:, k]
+        status[(status == OK) & ~(xPx > dtype(COLLINEAR_TOL) * ssx)] = COLLINEAR
+        df = n - c - 1
+        xPy = t[:, c - 1:].T                                  # [P, rows]
+        beta = xPy / xPx
+        s2r = (yy[:, None] - beta * xPy) / dtype(df)
+        se = np.sqrt(s2r / xPx)
+        T = beta / se
+        p = 2 * scipy.stats.t.sf(np.abs(T.astype(np.float64)), df)
+    bad = status != OK
+    for a in (beta, se, T, p):
+        a[:, bad] = np.nan
+    return dict(n_mis=nm.astype(np.int32), n_obs=n_obs.astype(np.int32), status=status, af=(dtype(0.5) * mu),
+                beta=beta, se=se, tstat=T, p=p, ssx=ssx, xPx=xPx, df=df)
+
+
+def products(g, miss, V, dtype=np.float64, grouped=False):
+    """D [rows, cols] = sum over observed calls of g V, Mm = sum over missing calls of V, and
+    A = sum |g V| (the scale of the dot-product bound)."""
+    V = np.asarray(V, dtype=dtype)
+    gT = np.asarray(g).T.astype(dtype)[:, :, None]             # [n_total, rows, 1]
+    mT = np.asarray(miss).T.astype(dtype)[:, :, None]
+    Vb = V[:, None, :]
+    return fsum(gT * Vb, grouped), fsum(mT * Vb, grouped), fsum(np.abs(gT * Vb), grouped), fsum(np.abs(mT * Vb), grouped)
+
+
+def scan(bed, n_total, pheno, covar=None, keep=None, rows=None, dtype=np.float64, grouped=False, V=None):
+    """The whole scan of the listed rows.  V: use these columns (n_total x (c - 1 + P)) in place of the
+    design's own (yy still the design's)."""
+    d = design(n_total, pheno, covar, keep, dtype)
+    g, miss = decode(bed, n_total, rows)
+    s = d["in_s"]
+    n1 = np.sum((g == 1) & s, axis=1)
+    n2 = np.sum((g == 2) & s, axis=1)
+    nm = np.sum(miss & s, axis=1)
+    D, Mm, absD, absM = products(g, miss, d["V"] if V is None else V, dtype, grouped)
+    with np.errstate(all="ignore"):
+        mu = (n1 + 2 * n2).astype(dtype) / (d["n"] - nm).astype(dtype)
+    t = D + np.where(np.isfinite(mu), mu, 0)[:, None] * Mm
+    out = finish(d["n"], d["c"], n1, n2, nm, t, d["yy"], dtype)
+    out.update(prod_d=D, prod_m=Mm, abs_d=absD, abs_m=absM, design=d, g=g, miss=miss)
+    return out
