@@ -149,3 +149,41 @@ def scan(bed, n_total, pheno, covar=None, keep=None, rows=None, dtype=np.float64
     out = finish(d["n"], d["c"], n1, n2, nm, t, d["yy"], dtype)
     out.update(prod_d=D, prod_m=Mm, abs_d=absD, abs_m=absM, design=d, g=g, miss=miss)
     return out
+
+
+def measured(bed, n_total, pheno, covar=None, keep=None, rows=None):
+    """The reference of a measured comparison and its yardsticks: (ref, ok, yard).  ref is the fp64
+    sequential scan, ok its OK rows; yard[k], k in beta / se / tstat, is the larger of ref's deviation
+    from the longdouble run and from the grouped order of summation (beta normwise per trait, se and T
+    elementwise relative over the OK rows).  Asserts the preconditions of such a comparison from the
+    reference alone: the three runs agree on the status, and every OK row has n_obs >= c + 2 and
+    xPx / ssx >= 1e-3, so no row sits near the COLLINEAR threshold."""
+    ref = scan(bed, n_total, pheno, covar, keep, rows)
+    ref_g = scan(bed, n_total, pheno, covar, keep, rows, grouped=True)
+    ref_l = scan(bed, n_total, pheno, covar, keep, rows, dtype=np.longdouble)
+    ok = ref["status"] == OK
+    assert np.array_equal(ref_l["status"], ref["status"]) and np.array_equal(ref_g["status"], ref["status"])
+    assert ok.sum() >= 1 and np.all(ref["n_obs"][ok] >= ref["design"]["c"] + 2)
+    assert np.all(ref["xPx"][ok] / ref["ssx"][ok] >= 1e-3)
+    yard = {}
+    for k in ("beta", "se", "tstat"):
+        a, b, l = (np.asarray(r[k][:, ok], dtype=np.longdouble) for r in (ref, ref_g, ref_l))
+        if k == "beta":
+            sc = np.max(np.abs(l), axis=1, keepdims=True)
+            yard[k] = max(float(np.max(np.abs(a - l) / sc)), float(np.max(np.abs(a - b) / sc)))
+        else:
+            yard[k] = max(float(np.max(np.abs(a / l - 1))), float(np.max(np.abs(a / b - 1))))
+    return ref, ok, yard
+
+
+def deviation(got, ref, ok, keys=("beta", "se", "tstat")):
+    """The measured deviation of got's beta (normwise per trait), se and tstat (elementwise relative)
+    from ref's over the OK rows: what is held to 32 yardsticks."""
+    dev = {}
+    for k in keys:
+        a, r = got[k][:, ok], ref[k][:, ok]
+        if k == "beta":
+            dev[k] = float(np.max(np.max(np.abs(a - r), axis=1) / np.max(np.abs(r), axis=1)))
+        else:
+            dev[k] = float(np.max(np.abs(a / r - 1)))
+    return dev

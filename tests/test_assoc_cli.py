@@ -84,6 +84,136 @@ def check_rows(rows, ref, q, precise):
             assert all(abs(a - b) <= 5.0001e-7 * abs(b) for a, b in zip(got[1:], want[1:])), (j, got, want)   # %e
 
 
+def held_to_the_reference(got, ref, ok, yard, what):
+    """The bars of test_assoc.py: integers, status and af exact; beta (normwise per trait), se and T
+    (elementwise) within max(32 x yardstick, 2^-48).  got may lack tstat (the file does not hold it)."""
+    for k in ("n_mis", "n_obs", "status"):
+        assert np.array_equal(got[k], ref[k]), (what, k)
+    assert np.array_equal(np.isnan(got["af"]), np.isnan(ref["af"])), what
+    assert np.array_equal(got["af"][ok].view(np.uint64), ref["af"][ok].view(np.uint64)), what
+    keys = [k for k in ("beta", "se", "tstat") if k in got]
+    dev = AR.deviation(got, ref, ok, keys)
+    print(f"assoc cli {what}: yardstick beta {yard['beta']:.2e} se {yard['se']:.2e} T {yard['tstat']:.2e}; "
+          + " ".join(f"{k} {dev[k]:.2e}" for k in keys) + f"; OK rows {int(ok.sum())}")
+    for k in keys:
+        assert np.all(np.isfinite(got[k][:, ok])) and dev[k] <= max(32 * yard[k], 2.0 ** -48), (what, k, dev[k], yard[k])
+
+
+@gpu
+def test_the_library_scan_of_the_panel_is_the_references(panel, scan):
+    """The `scan` the CLI is compared with, held to tests/_assoc_ref.py on the module's 600 x 300 panel (38
+    tiles in 10 workgroups, three finish blocks) with the bars of test_assoc.py; the preconditions
+    (n_obs >= c + 2 and xPx / ssx >= 1e-3 on every OK row) are asserted from the reference first."""
+    ref, ok, yard = AR.measured(panel["bed"], N, np.column_stack([panel["y"], panel["y2"]]), panel["w"])
+    assert ref["status"][MONO] == AR.MONOMORPHIC and ok.sum() == M - 1
+    held_to_the_reference(scan, ref, ok, yard, "600 x 300")
+    assert np.all(np.isnan(scan["beta"][:, ~ok]))
+
+
+def file_scan(paths, n_rows, names):
+    """The outputs a set of --precise-out files (one per trait) holds, in the layout of `assoc`: rows absent
+    from the files have status -1 and NaN."""
+    P = len(paths)
+    out = dict(n_mis=np.zeros(n_rows, dtype=np.int32), n_obs=np.zeros(n_rows, dtype=np.int32),
+               status=np.full(n_rows, -1, dtype=np.int32), af=np.full(n_rows, np.nan),
+               beta=np.full((P, n_rows), np.nan), se=np.full((P, n_rows), np.nan), p=np.full((P, n_rows), np.nan))
+    at = {s: j for j, s in enumerate(names)}
+    for q, path in enumerate(paths):
+        for r in read_assoc(path):
+            j = at[r[1]]
+            assert q == 0 or (out["n_mis"][j], out["n_obs"][j], out["af"][j]) == (int(r[3]), int(r[4]), float(r[7]))
+            out["n_mis"][j], out["n_obs"][j], out["status"][j], out["af"][j] = int(r[3]), int(r[4]), 0, float(r[7])
+            out["beta"][q, j], out["se"][q, j], out["p"][q, j] = float(r[8]), float(r[9]), float(r[10])
+    return out
+
+
+@gpu
+def test_assoc_two_panels_are_written_one_after_the_other(panel):
+    """-r A,B with B a second panel of the same individuals (100 other rows, one monomorphic): A's lines, then
+    B's, each half the single-panel run's line for line; .assoc.skipped lists both panels' rows in order;
+    and B's half holds the reference's integers, af, beta and se."""
+    d = panel["dir"]
+    mb, mono_b = 100, 31
+    rng = np.random.default_rng(12)
+    g = rng.binomial(2, rng.uniform(0.2, 0.5, size=(mb, 1)), size=(mb, N)).astype(np.int8)
+    m = rng.random((mb, N)) < 0.02
+    g[mono_b], m[mono_b] = 2, rng.random(N) < 0.1
+    pre_b = os.path.join(d, "second")
+    bed_b = AR.encode(g, m)
+    bed_b.tofile(pre_b + ".bed")
+    with open(pre_b + ".fam", "w") as f:
+        f.write(open(panel["pre"] + ".fam").read())
+    with open(pre_b + ".bim", "w") as f:
+        for j in range(mb):
+            f.write(f"2\tsb{j}\t0\t{500 + 10 * j}\tC\tT\n")
+    lines, skipped = {}, {}
+    for key, r_arg in (("a", panel["pre"]), ("b", pre_b), ("ab", panel["pre"] + "," + pre_b)):
+        out = os.path.join(d, "two_" + key)
+        r = run(["--assoc", "-r", r_arg, "--out", out, "--covar", panel["pre"] + ".covar", "--precise-out"], d)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines[key] = open(out + ".assoc.txt").read().splitlines()
+        skipped[key] = open(out + ".assoc.skipped").read().splitlines()
+    assert len(lines["a"]) == M - 1 and len(lines["b"]) == mb - 1
+    assert lines["ab"] == lines["a"] + lines["b"]
+    assert skipped["ab"] == skipped["a"] + skipped["b"] == [f"rs{MONO}\tmonomorphic", f"sb{mono_b}\tmonomorphic"]
+    ref, ok, yard = AR.measured(bed_b, N, panel["y"], panel["w"])
+    names = [f"sb{j}" for j in range(mb)]
+    got = file_scan([os.path.join(d, "two_b.assoc.txt")], mb, names)
+    assert np.array_equal(got["status"] == 0, ok) and ref["status"][mono_b] == AR.MONOMORPHIC
+    for k in ("n_mis", "n_obs"):
+        got[k][~ok] = ref[k][~ok]                               # (skipped rows are not in the file)
+    got["status"][~ok] = ref["status"][~ok]
+    got["af"][~ok] = ref["af"][~ok]
+    held_to_the_reference(got, ref, ok, yard, "second panel, 100 x 300")
+
+
+@gpu
+def test_assoc_sample_selection_reaches_the_scan(panel):
+    """--keep, and --pheno with one NA, one -9, one individual without a line and one duplicate line (the
+    first wins), with --covar: the printed n is the reference's, and the --precise-out files hold the
+    integers and af of tests/_assoc_ref.py on the corresponding keep / NaN arrays, beta and se within the
+    bars of test_assoc.py."""
+    d = panel["dir"]
+    rng = np.random.default_rng(13)
+    keep = (rng.random(N) < 0.9).astype(np.uint8)
+    keep[[0, 15, 16, 63, 64, 255, 256, N - 1]] = (0, 1, 0, 0, 1, 0, 1, 0)
+    i_na, i_m9, i_absent, i_dup = (int(i) for i in np.flatnonzero(keep)[[10, 40, 90, 150]])
+    Y = np.column_stack([panel["y"], panel["y2"]])
+    with open(os.path.join(d, "sel.keep"), "w") as f:
+        for i in range(N):
+            f.write(f"{int(keep[i])}\n")
+    with open(os.path.join(d, "sel.pheno"), "w") as f:
+        for i in range(N):
+            v = [repr(float(Y[i, 0])), repr(float(Y[i, 1]))]
+            if i == i_absent:
+                continue
+            if i == i_na:
+                v[0] = "NA"
+            if i == i_m9:
+                v[1] = "-9"
+            f.write(f"F{i} I{i} {v[0]} {v[1]}\n")
+        f.write(f"F{i_dup} I{i_dup} 99.5 NA\n")                 # a second line of i_dup, after its first: ignored
+    Yn = Y.copy()
+    Yn[i_na, 0] = Yn[i_m9, 1] = np.nan
+    Yn[i_absent] = np.nan
+    ref, ok, yard = AR.measured(panel["bed"], N, Yn, panel["w"], keep)
+    n = ref["design"]["n"]
+    assert n == int(keep.sum()) - 3
+    out = os.path.join(d, "sel")
+    r = run(["--assoc", "-r", panel["pre"], "--out", out, "--covar", panel["pre"] + ".covar", "--keep",
+             os.path.join(d, "sel.keep"), "--pheno", os.path.join(d, "sel.pheno"), "--pheno-col", "1,2", "--precise-out"], d)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert f"assoc: n {n} of {N} individuals, c 3, P 2, {M} rows" in r.stdout, r.stdout
+    got = file_scan([f"{out}.{q + 1}.assoc.txt" for q in (0, 1)], M, [f"rs{j}" for j in range(M)])
+    assert np.array_equal(got["status"] == 0, ok)
+    want = [f"rs{j}\t" + {AR.NO_CALL: "no_call", AR.MONOMORPHIC: "monomorphic", AR.COLLINEAR: "collinear"}[int(ref["status"][j])]
+            for j in np.flatnonzero(~ok)]
+    assert open(out + ".assoc.skipped").read().splitlines() == want and f"rs{MONO}\tmonomorphic" in want
+    for k in ("n_mis", "n_obs", "status", "af"):
+        got[k][~ok] = ref[k][~ok]                               # (skipped rows are not in the files)
+    held_to_the_reference(got, ref, ok, yard, "keep + pheno + covar")
+
+
 @gpu
 def test_assoc_writes_gemmas_columns(panel, scan):
     out = os.path.join(panel["dir"], "a")
